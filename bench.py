@@ -2,15 +2,23 @@
 """SMT-phase training throughput of LLaMA-3-8B SMT(0.71%) on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]      # N > 1: starts N ranks itself
+    python bench.py --full [...]                             # + every side measurement (below)
+    python bench.py --dump-outputs DIR [...]                 # + the last timed step's results as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs: steps 1-3 below, the W untimed and K timed steps of
+step 4, and the JSON line (the side measurements' fields are null in it). ``--full`` adds the rest:
+the per-kernel HIP-event timers and rooflines, the other activation / rounding / selection points
+and the CPU baseline. ``--dump-outputs DIR`` writes what the last timed step left with its caller
+(the loss, the tile gradients and the updated tiles; ``dump_outputs``) right after the timed steps.
 
 One process per GPU (RCCL over xGMI for N > 1, weak scaling: B=16 x S=2048 per GPU). Per rank:
 
 1. LLaMA-3-8B architecture (HF ``LlamaForCausalLM``), random init (seed 1234), bf16, synthetic
    uniform token batches, labels = input ids. Gradient checkpointing (fine_tune.py:192) is on for
    the full-FT warm-up; in the SMT phase the activations stay resident in HBM (its peak is then
-   still below the warm-up's), and a short second measurement with checkpointing on (the
+   still below the warm-up's), and with ``--full`` a second measurement with checkpointing on (the
    reference's memory policy) is reported under ``grad_ckpt_mode``.
 2. Warm-up: ``--full-ft-steps`` full fine-tuning steps through the engine (fp32-master AdamW over
    all 8.03 B params) with the gradient harvest of fine_tune.py:714-767 in HBM.
@@ -21,10 +29,11 @@ One process per GPU (RCCL over xGMI for N > 1, weak scaling: B=16 x S=2048 per G
    bracketed by barrier + synchronize; the max over ranks is reported. ``value`` is the K steps'
    tokens over their wall time; HIP events at the step boundaries also give the median step
    (BASELINE.md's definition: median over steps 10-60 after the conversion = the defaults).
-   The reference's memory policy (per-layer recompute) is then timed over as many steps
-   (``grad_ckpt_mode``).
+   With ``--full`` the reference's memory policy (per-layer recompute) is then timed over as many
+   steps (``grad_ckpt_mode``).
 
-Rank 0 prints ONE JSON line. ``roofline`` is for the dominant hand-written kernel (the tile
+Rank 0 prints ONE JSON line. The rest of this paragraph is ``--full``'s.
+``roofline`` is for the dominant hand-written kernel (the tile
 wgrad: smt_tile_wgrad_batch / smt_tile_wgrad = wgrad_dma | wgrad_quarter + wgrad_reduce), timed
 with HIP events on its launch stream over extra steps with the wgrad stream joined (the kernel
 alone); its algorithmic bytes count each distinct operand slice of a launch once, and the roof
@@ -80,6 +89,15 @@ def parse():
     # defaults: BASELINE.md's definition, steps 10-60 after the conversion (10 untimed, 50 timed)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement: the per-kernel HIP-event "
+                         "timers and rooflines, the other activation / rounding / selection points (the "
+                         "--*-steps options below) and the CPU baseline. Without it those options default to 0 "
+                         "and their fields of the JSON line are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them left with its caller as "
+                         "DIR/<name>.npy (float32): loss, tile_grads, tile_weights (a fixed seeded sample of "
+                         "each above DUMP_SAMPLE_ELEMS elements); same arguments, same inputs")
     ap.add_argument("--model", default="llama3-8b", choices=sorted(MODELS))
     ap.add_argument("--batch", type=int, default=16, help="per-GPU micro batch (deepspeed/README.md:39)")
     ap.add_argument("--seq", type=int, default=2048)
@@ -148,11 +166,12 @@ def parse():
     ap.add_argument("--no-overlap-wgrad", action="store_true",
                     help="run the tile weight gradients on the current stream (default: their own stream, "
                          "overlapped with the data-gradient GEMMs)")
-    ap.add_argument("--roofline-steps", type=int, default=5,
+    ap.add_argument("--roofline-steps", type=int, default=None,
                     help="extra SMT steps after the timed region with the wgrad stream joined, on which the "
                          "tile-wgrad roofline is measured (the kernel alone; in the timed region it shares the "
-                         "chip with the data-gradient GEMM)")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0, help="0 disables the CPU leg")
+                         "chip with the data-gradient GEMM); default with --full: 5")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=None,
+                    help="default with --full: 15; 0 disables the CPU leg")
     ap.add_argument("--out", default=None, help="also write the JSON line here")
     ap.add_argument("--dist-backend", default=None,
                     help="nccl (= RCCL on ROCm; the default with N > 1) or gloo (functional tests). Given with "
@@ -163,20 +182,15 @@ def parse():
     default_ratio = (0.0043 if args.fp8 else 0.00356) if args.model == "llama3-8b" else 0.03
     args.att_ratio = default_ratio if args.att_ratio is None else args.att_ratio
     args.mlp_ratio = default_ratio if args.mlp_ratio is None else args.mlp_ratio
-    if args.ref_mode_steps is None:
-        args.ref_mode_steps = args.steps
-    if args.selective_steps is None:
-        args.selective_steps = args.steps
-    if args.views_steps is None:
-        args.views_steps = args.steps
-    if args.half_resident_steps is None:
-        args.half_resident_steps = min(args.steps, 20)
-    if args.ref_rounding_steps is None:
-        args.ref_rounding_steps = min(args.steps, 20)
-    if args.no_transposed_steps is None:
-        args.no_transposed_steps = min(args.steps, 20)
-    if args.raw_harvest_steps is None:
-        args.raw_harvest_steps = min(args.steps, 20)
+    # the side measurements: their defaults hold under --full; a plain run leaves them out (0) unless
+    # one is asked for by its own option
+    for name, default in (("ref_mode_steps", args.steps), ("selective_steps", args.steps),
+                          ("views_steps", args.steps), ("half_resident_steps", min(args.steps, 20)),
+                          ("ref_rounding_steps", min(args.steps, 20)), ("no_transposed_steps", min(args.steps, 20)),
+                          ("raw_harvest_steps", min(args.steps, 20)), ("roofline_steps", 5),
+                          ("cpu_baseline_seconds", 15.0)):
+        if getattr(args, name) is None:
+            setattr(args, name, default if args.full else 0)
     return args
 
 
@@ -867,6 +881,30 @@ def timed_steps(step, batch_list, world, device):
     return elapsed, per_step, loss
 
 
+DUMP_SAMPLE_ELEMS = 1 << 22       # per dumped array: 16 MB of float32
+
+
+@torch.no_grad()
+def dump_outputs(path, loss, engine):
+    """--dump-outputs: what the last timed step (forward + engine.backward + engine.step) left with its
+    caller, as ``path/<name>.npy`` in float32: ``loss`` (the value ``step`` returns), ``tile_grads`` (the
+    fp32 gradients of every ``selected_weight``, as ``engine.tile_grad`` hands them out, in the engine's
+    packed tile order) and ``tile_weights`` (the tiles after the fused AdamW). An array of more than
+    DUMP_SAMPLE_ELEMS elements is written as a sample at fixed (seed 1234) sorted positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    if engine.tile_groups:
+        scale = engine._grad_scale()
+        arrays["tile_grads"] = torch.cat([tg.grad.reshape(-1) for tg in engine.tile_groups]) * scale
+        arrays["tile_weights"] = torch.cat([tg.param.reshape(-1) for tg in engine.tile_groups]).float()
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE_ELEMS,), generator=torch.Generator().manual_seed(1234))
+            t = t[idx.sort().values.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     if os.environ.get("SMT_BENCH_STACKS"):
@@ -917,17 +955,18 @@ def main():
     from sparse_matrix_tuning_amd.engine import SMTFusedAdam, initialize
     from sparse_matrix_tuning_amd import trainer
 
-    timer = WgradTimer()
-    install_wgrad_timer(timer)
-    install_wgrad_batch_timer(timer)
-    mx_timer = WgradTimer()
-    install_mx_wgrad_timer(mx_timer)
-    install_mx_wgrad_batch_timer(mx_timer)
-    atimer = AttnTimer()
-    if not (args.eager_ops or args.sdpa_attention):
-        install_attn_timer(atimer)
-    adam_timer = LaunchTimer()
-    install_adam_timer(adam_timer)
+    # the per-kernel HIP-event timers belong to the side measurements: a plain run leaves the product's
+    # launch functions as they are (the summaries are then None)
+    kernel_timers = args.full or args.roofline_steps > 0
+    timer, mx_timer, atimer, adam_timer = WgradTimer(), WgradTimer(), AttnTimer(), LaunchTimer()
+    if kernel_timers:
+        install_wgrad_timer(timer)
+        install_wgrad_batch_timer(timer)
+        install_mx_wgrad_timer(mx_timer)
+        install_mx_wgrad_batch_timer(mx_timer)
+        if not (args.eager_ops or args.sdpa_attention):
+            install_attn_timer(atimer)
+        install_adam_timer(adam_timer)
     sel_timer = SelectionTimer()
     sel_timer.install()
 
@@ -1058,6 +1097,9 @@ def main():
     adam = adam_timer.summary()
     del smt_batches
     log(f"timed: {value:.1f} tokens/s ({elapsed / args.steps * 1e3:.1f} ms/step), peak {peak[0].item():.1f} GB")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, engine)
+        log(f"last timed step's outputs written to {args.dump_outputs}")
 
     # ---- the tile wgrad alone (its roofline): the same steps with the wgrad stream joined ----
     overlapped = {"bf16": w, "mx": w_mx}
@@ -1305,7 +1347,7 @@ def main():
         out = {
             "metric": METRIC, "value": round(value, 1), "unit": "tokens/s", "n_gpus": world,
             "world_size": dist.get_world_size() if dist.is_initialized() else 1, "backend": backend, "devices_used": devices_used,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
+            "steps": args.steps, "warmup": args.warmup, "full": bool(args.full), "ms_per_step": round(elapsed / args.steps * 1e3, 2),
             "median_ms_per_step": round(med * 1e3, 2), "median_tokens_per_s": round(world * B * S / med, 1),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "fp8-e4m3 (rowwise-scaled decoder GEMMs) + bf16" if args.fp8 else "bf16",

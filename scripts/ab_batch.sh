@@ -5,7 +5,7 @@ set -o pipefail
 OUT=gpurun_out/${TAG:-ab}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-COMMON="--cpu-baseline-seconds 0 --ref-mode-steps 0 --steps ${STEPS:-30}"
+COMMON="--full --cpu-baseline-seconds 0 --ref-mode-steps 0 --steps ${STEPS:-30}"
 for mode in ${MODES:-fp8 bf16}; do
   extra=""; [ "$mode" = fp8 ] && extra="--fp8"
   for bt in ${BATCH_TILES:-0 48}; do

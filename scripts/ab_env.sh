@@ -5,7 +5,7 @@ set -o pipefail
 OUT=gpurun_out/${TAG:-abenv}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-COMMON="--cpu-baseline-seconds 0 --ref-mode-steps 0 --steps ${STEPS:-10} --warmup 3 ${BENCH_ARGS:-}"
+COMMON="--full --cpu-baseline-seconds 0 --ref-mode-steps 0 --steps ${STEPS:-10} --warmup 3 ${BENCH_ARGS:-}"
 i=0
 for v in ${VARIANTS:-base}; do
   i=$((i+1))

@@ -60,6 +60,58 @@ def test_nccl_ranks_beyond_devices_refused():
     assert "need 2 GPUs" in r.stderr
 
 
+SIDE_LEGS = ("ref_mode_steps", "selective_steps", "views_steps", "half_resident_steps", "ref_rounding_steps",
+             "no_transposed_steps", "raw_harvest_steps", "roofline_steps", "cpu_baseline_seconds")
+
+
+def _parse(monkeypatch, *argv):
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    return bench.parse()
+
+
+def test_plain_run_leaves_the_side_measurements_out(monkeypatch):
+    """A plain run times its steps and nothing else; ``--full`` brings back the defaults the side
+    measurements had; one asked for by its own option runs either way."""
+    a = _parse(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert {k: getattr(a, k) for k in SIDE_LEGS} == dict.fromkeys(SIDE_LEGS, 0)
+    f = _parse(monkeypatch, "--full", "--steps", "30")
+    assert [getattr(f, k) for k in SIDE_LEGS] == [30, 30, 30, 20, 20, 20, 20, 5, 15.0]
+    f = _parse(monkeypatch, "--full", "--steps", "7", "--cpu-baseline-seconds", "0")
+    assert [getattr(f, k) for k in SIDE_LEGS] == [7, 7, 7, 7, 7, 7, 7, 5, 0.0]
+    one = _parse(monkeypatch, "--ref-mode-steps", "4")
+    assert one.ref_mode_steps == 4 and one.selective_steps == 0 and one.cpu_baseline_seconds == 0
+
+
+def test_dump_outputs_writes_float32_arrays_with_a_fixed_sample(monkeypatch, tmp_path):
+    import types
+
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ELEMS", 1000)
+    groups = [types.SimpleNamespace(grad=torch.arange(0, 3000, dtype=torch.float32),
+                                    param=torch.arange(0, 3000, dtype=torch.float32).bfloat16()),
+              types.SimpleNamespace(grad=torch.arange(3000, 3600, dtype=torch.float32),
+                                    param=torch.zeros(600, dtype=torch.bfloat16))]
+    engine = types.SimpleNamespace(tile_groups=groups, _grad_scale=lambda: 0.5)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(2.5, dtype=torch.bfloat16), engine)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "tile_grads", "tile_weights")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["loss.npy", "tile_grads.npy", "tile_weights.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"].tolist() == [2.5]
+    g = got["tile_grads"]                       # 0.5 x the position: the sample's positions, sorted, both groups
+    assert g.shape == (1000,) and np.all(np.diff(g) >= 0) and g.max() > 1500 and np.all(g * 2 == np.round(g * 2))
+    idx = (g * 2).astype(np.int64)
+    full = torch.cat([t.param for t in groups]).float().numpy()
+    assert np.array_equal(got["tile_weights"], full[idx])
+    for n, v in got.items():                    # the same positions in every run
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy"))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ELEMS", 1 << 22)
+    bench.dump_outputs(str(tmp_path / "c"), torch.tensor(1.0), engine)
+    assert np.array_equal(np.load(tmp_path / "c" / "tile_grads.npy"), 0.5 * np.arange(3600, dtype=np.float32))
+
+
 def test_memory_vs_full_ft_reports_both_transposed_settings():
     """the reference's one published figure (README.md:5, 67 % less GPU memory than
     full fine-tuning) reported at the recompute policy with and without the W^T copies, tokens/s beside
