@@ -798,6 +798,13 @@ int launch_bwd_dw(const void* dres, int64_t lddr, const void* dy, int64_t lddy, 
                                  : fail(-1, "%s: dtype %d is not a 16-bit format (SMT_DTYPE_BF16 / SMT_DTYPE_FP16)", \
                                         what, (int)(dtype)))
 
+// The dtype is validated before anything else, so that an empty input (rows == 0 / n == 0, a no-op)
+// with a dtype that is not a 16-bit format is refused like a non-empty one (include/smt_model_ops.h).
+int check_fmt(const char* what, int32_t dtype) {
+    if (dtype == SMT_DTYPE_BF16 || dtype == SMT_DTYPE_FP16) return 0;
+    return fail(-1, "%s: dtype %d is not a 16-bit format (SMT_DTYPE_BF16 / SMT_DTYPE_FP16)", what, (int)dtype);
+}
+
 template <int F>
 int ce_fwd_impl(const void* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t vocab, int64_t ignore_index,
                 float* lse, float* loss, hipStream_t stream) {
@@ -902,6 +909,7 @@ const char* smt_model_ops_last_error(void) { return g_err; }
 
 int smt_ce_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t vocab,
                int64_t ignore_index, float* lse, float* loss, int32_t dtype, hipStream_t stream) {
+    if (check_fmt("smt_ce_fwd", dtype)) return -1;
     if (rows < 0 || vocab <= 0 || (vocab & 7) || ld < vocab)
         return fail(-1, "smt_ce_fwd: bad sizes rows=%lld vocab=%lld ld=%lld (vocab %% 8 == 0, ld >= vocab)",
                     (long long)rows, (long long)vocab, (long long)ld);
@@ -915,6 +923,7 @@ int smt_ce_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_t ro
 int smt_ce_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* scale,
                int64_t rows, int64_t vocab, int64_t ignore_index, void* dlogits, int64_t ld_d, int32_t dtype,
                hipStream_t stream) {
+    if (check_fmt("smt_ce_bwd", dtype)) return -1;
     if (rows < 0 || vocab <= 0 || (vocab & 7) || ld < vocab || ld_d < vocab)
         return fail(-1, "smt_ce_bwd: bad sizes rows=%lld vocab=%lld", (long long)rows, (long long)vocab);
     if (rows == 0) return 0;
@@ -929,6 +938,7 @@ int smt_ce_bwd(const void* logits, int64_t ld, const int64_t* labels, const floa
 
 int smt_rmsnorm_fwd(const void* x, int64_t ld_x, const void* weight, void* y, int64_t ld_y, float* rstd,
                     int64_t rows, int32_t hidden, float eps, int32_t dtype, hipStream_t stream) {
+    if (check_fmt("smt_rmsnorm_fwd", dtype)) return -1;
     if (rows < 0 || hidden <= 0 || (hidden & 7)) return fail(-1, "smt_rmsnorm_fwd: bad sizes rows=%lld hidden=%d", (long long)rows, hidden);
     if (rows == 0) return 0;
     if (!x || !weight || !y || !rstd) return fail(-1, "smt_rmsnorm_fwd: null pointer");
@@ -973,6 +983,7 @@ int smt_rmsnorm_fwd_quant_e4m3(const void* x, int64_t ld_x, const void* residual
 int smt_add_rmsnorm_fwd(const void* x, int64_t ld_x, const void* residual, int64_t ld_r, const void* weight, void* h,
                         int64_t ld_h, void* y, int64_t ld_y, float* rstd, int64_t rows, int32_t hidden, float eps,
                         int32_t dtype, hipStream_t stream) {
+    if (check_fmt("smt_add_rmsnorm_fwd", dtype)) return -1;
     if (rows < 0 || hidden <= 0 || hidden % 512 || hidden > 8192)
         return fail(-1, "smt_add_rmsnorm_fwd: hidden %d must be a multiple of 512, <= 8192", hidden);
     if (rows == 0) return 0;
@@ -987,6 +998,7 @@ int smt_add_rmsnorm_fwd(const void* x, int64_t ld_x, const void* residual, int64
 int smt_rmsnorm_bwd_add(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, const void* weight, const float* rstd,
                         const void* dres, int64_t ld_dres, void* dx, int64_t ld_dx, int64_t rows, int32_t hidden,
                         int32_t dtype, hipStream_t stream) {
+    if (check_fmt("smt_rmsnorm_bwd_add", dtype)) return -1;
     if (rows < 0 || hidden <= 0 || hidden % 512 || hidden > 8192)
         return fail(-1, "smt_rmsnorm_bwd_add: hidden %d must be a multiple of 512, <= 8192", hidden);
     if (rows == 0) return 0;
@@ -1035,6 +1047,7 @@ int smt_rmsnorm_bwd_waves(int64_t rows) {
 int smt_rmsnorm_bwd(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, const void* weight, const float* rstd,
                     void* dx, int64_t ld_dx, float* dw_partial, void* dw, int64_t rows, int32_t hidden, int32_t dtype,
                     hipStream_t stream) {
+    if (check_fmt("smt_rmsnorm_bwd", dtype)) return -1;
     if (rows < 0 || hidden <= 0 || (hidden & 7)) return fail(-1, "smt_rmsnorm_bwd: bad sizes");
     if (rows == 0) return 0;
     if (!dy || !x || !weight || !rstd || !dx) return fail(-1, "smt_rmsnorm_bwd: null pointer");
@@ -1048,6 +1061,7 @@ int smt_rmsnorm_bwd_add_dw(const void* dy, int64_t ld_dy, const void* x, int64_t
                            const float* rstd, const void* dres, int64_t ld_dres, void* dx, int64_t ld_dx,
                            float* dw_partial, void* dw, int64_t rows, int32_t hidden, int32_t dtype,
                            hipStream_t stream) {
+    if (check_fmt("smt_rmsnorm_bwd_add_dw", dtype)) return -1;
     if (rows < 0 || hidden <= 0 || (hidden & 7)) return fail(-1, "smt_rmsnorm_bwd_add_dw: bad sizes");
     if (rows == 0) return 0;
     if (!dy || !x || !weight || !rstd || !dx || !dres) return fail(-1, "smt_rmsnorm_bwd_add_dw: null pointer");
@@ -1060,6 +1074,7 @@ int smt_rmsnorm_bwd_add_dw(const void* dy, int64_t ld_dy, const void* x, int64_t
 
 static int rope(bool bwd, const smt_rope_tensor* q, const smt_rope_tensor* k, const void* cos, const void* sin,
                 int64_t cos_sb, int64_t cos_ss, int64_t B, int32_t S, int32_t D, int32_t dtype, hipStream_t stream) {
+    if (check_fmt("smt_rope", dtype)) return -1;
     if (!q || !k || !cos || !sin) return fail(-1, "smt_rope: null pointer");
     if (B < 0 || S < 0 || D <= 0 || (D & 15)) return fail(-1, "smt_rope: head_dim %d must be a multiple of 16", D);
     RopeT tq{(const uint16_t*)q->in, (uint16_t*)q->out, q->in_sb, q->in_sh, q->in_ss, q->out_sb, q->out_sh, q->out_ss, q->heads};
@@ -1089,6 +1104,7 @@ int smt_rope_bwd(const smt_rope_tensor* dq, const smt_rope_tensor* dk, const voi
 }
 
 int smt_swiglu_fwd(const void* gate, const void* up, void* out, int64_t n, int32_t dtype, hipStream_t stream) {
+    if (check_fmt("smt_swiglu_fwd", dtype)) return -1;
     if (n < 0 || (n & 7)) return fail(-1, "smt_swiglu_fwd: n %lld must be a multiple of 8", (long long)n);
     if (n == 0) return 0;
     if (!aligned16(gate) || !aligned16(up) || !aligned16(out)) return fail(-2, "smt_swiglu_fwd: alignment");
@@ -1097,6 +1113,7 @@ int smt_swiglu_fwd(const void* gate, const void* up, void* out, int64_t n, int32
 
 int smt_swiglu_bwd(const void* gate, const void* up, const void* grad_out, void* grad_gate, void* grad_up, int64_t n,
                    int32_t dtype, hipStream_t stream) {
+    if (check_fmt("smt_swiglu_bwd", dtype)) return -1;
     if (n < 0 || (n & 7)) return fail(-1, "smt_swiglu_bwd: n %lld must be a multiple of 8", (long long)n);
     if (n == 0) return 0;
     if (!aligned16(gate) || !aligned16(up) || !aligned16(grad_out) || !aligned16(grad_gate) || !aligned16(grad_up))
@@ -1107,6 +1124,7 @@ int smt_swiglu_bwd(const void* gate, const void* up, const void* grad_out, void*
 int smt_colblock_recompute(int32_t op, const void* a, int64_t ld_a, const void* b, int64_t ld_b, const void* weight,
                            const float* rstd, int64_t T, const int32_t* col_blocks_dev, int32_t n_cb, void* out,
                            int32_t dtype, hipStream_t stream) {
+    if (check_fmt("smt_colblock_recompute", dtype)) return -1;
     if (op != SMT_RECOMPUTE_RMSNORM && op != SMT_RECOMPUTE_SWIGLU)
         return fail(-1, "smt_colblock_recompute: unknown op %d", (int)op);
     if (T < 0 || n_cb < 0 || ld_a < 0 || ld_b < 0) return fail(-1, "smt_colblock_recompute: negative size");

@@ -536,6 +536,10 @@ LM_HEAD_CHUNK_ROWS = int(os.environ.get("SMT_LM_HEAD_CHUNK_ROWS", "4096"))
 # profiles/r05_k_kernel_stats.csv). The chunk buffer is transient in the forward, below the warm-up's
 # peak (the backward's bf16 gradients of every parameter).
 LM_HEAD_DW_CHUNK_ROWS = int(os.environ.get("SMT_LM_HEAD_DW_CHUNK_ROWS", "16384"))
+# fp16 only: the forward's dlogits carry 2^(ceil(log2(denom)) + this) / denom, i.e. lie in [-32, 32]
+# (FusedLMHeadLossFn). dh = dlogits @ W is a p-weighted average of W's rows times that factor: below
+# 64 max|W|, three decades under fp16's 65504 for any head whose weights are below 1.
+LM_HEAD_FP16_HEADROOM_BITS = 4
 
 
 class FusedLMHeadLossFn(torch.autograd.Function):
@@ -558,8 +562,26 @@ class FusedLMHeadLossFn(torch.autograd.Function):
     Per row this is the unfused arithmetic: the same GEMM products, the same kernels and, for the
     upstream gradient 1 that ``loss.backward()`` gives (``engine.backward`` with one accumulation
     step), the same ``dlogits`` scale ``1 / denom``. Any other upstream gradient is applied to the
-    bf16 ``dh`` / ``dW`` (one more rounding than folding it into ``dlogits`` first, exact for powers
-    of two). Whether hipBLASLt picks the same kernel for a chunk's GEMM shape as for the whole batch's
+    16-bit ``dh`` / ``dW`` (one more rounding than folding it into ``dlogits`` first, exact for powers
+    of two while the result stays in the format's normal range).
+
+    bf16 has fp32's exponent range, so ``dlogits / denom`` survives its rounding whatever the upstream
+    gradient will be. fp16 does not: at N rows a non-label entry is about ``p / N``, below fp16's
+    smallest subnormal (6e-8) from N x V of a few million on, and the loss scale that exists to lift
+    it arrives only in the backward, after the rounding. (Applied to the fp16 ``dh`` by ``torch.mul``
+    it was also cast to fp16 first: 2^16, the engine's initial scale, became inf.) For fp16 the
+    forward therefore computes ``dlogits`` with the scale ``k / denom``, ``k = 2^(ceil(log2(denom))
+    + 4)`` taken from ``denom``'s exponent on the device (no host synchronisation): ``k / denom`` lies
+    in [16, 32), ``dlogits`` in [-32, 32] (eager's own values at loss scale 2^16 and N = 4096, 8 x
+    eager's at N = 32768). ``dh`` is an average of ``W``'s rows times that factor and cannot overflow;
+    ``dW`` is a sum over all rows, so its fp32 accumulator is rounded to fp16 under one shared
+    power-of-two exponent taken from its largest entry. The backward multiplies by ``dloss / k`` (and
+    that exponent) in fp32 and rounds once: an exact rescale for the power-of-two ``dloss`` a loss
+    scaler gives, so the one rounding that can lose range is the last one, at the magnitude eager
+    rounds at. Same kernels, same GEMMs, the chunked memory profile; the bf16 path is the ``k = 1``
+    case and is not touched (tests/test_gpu_fp16_loss_scale.py).
+
+    Whether hipBLASLt picks the same kernel for a chunk's GEMM shape as for the whole batch's
     decides bit-identity of the logits and ``dh``; ``dW`` sums the same fp32 products in chunk order
     before its one rounding. tests/test_gpu_cross_entropy.py checks both."""
 
@@ -587,7 +609,17 @@ class FusedLMHeadLossFn(torch.autograd.Function):
         lse = torch.empty(N, dtype=torch.float32, device=hidden.device)
         rows = torch.empty(N, dtype=torch.float32, device=hidden.device)
         dh = torch.empty((N, H), dtype=hidden.dtype, device=hidden.device) if need_dh else None
-        scale = (1.0 / denom.to(torch.float32)).reshape(1).contiguous()
+        denom32 = denom.to(torch.float32)
+        prescale = None
+        if hidden.dtype == torch.float16:
+            # k = 2^(ceil(log2(denom)) + LM_HEAD_FP16_HEADROOM_BITS) from denom's exponent field, on the
+            # device: k / denom lies in [16, 32)
+            mant, expo = torch.frexp(denom32)
+            expo = expo - (mant == 0.5).to(expo.dtype) + LM_HEAD_FP16_HEADROOM_BITS
+            prescale = _pow2(expo)
+            scale = (prescale / denom32).reshape(1).contiguous()
+        else:
+            scale = (1.0 / denom32).reshape(1).contiguous()
         C = max(1, min(max(int(chunk_rows), LM_HEAD_DW_CHUNK_ROWS if need_dw else 0), N))
         buf = torch.empty((C, V), dtype=hidden.dtype, device=hidden.device)
         w_dgrad = weight_t.t() if weight_t is not None else weight
@@ -612,21 +644,52 @@ class FusedLMHeadLossFn(torch.autograd.Function):
                 else:
                     torch.addmm(acc, lg.t(), hc, out_dtype=torch.float32, out=acc)
         del buf
-        dw = None
-        if need_dw:
+        dw = dw_prescale = None
+        if need_dw and prescale is not None:
+            # fp16: dW sums N rows of dlogits x hidden (not an average like dh), so its magnitude is
+            # not known before the sum is. It is kept as fp16 under one shared power-of-two exponent
+            # taken from the accumulator's largest entry (that entry lands in [2^14, 2^15))
+            lo, hi = torch.aminmax(acc)
+            _m, e = torch.frexp(torch.maximum(hi, -lo))
+            shift = _pow2(torch.clamp(15 - e, min=-112, max=60))
+            dw = acc.mul_(shift).to(weight.dtype)
+            dw_prescale = prescale * shift
+            del acc
+        elif need_dw:
             dw = acc.to(weight.dtype)
             del acc
-        ctx.save_for_backward(dh, dw)
+        ctx.save_for_backward(dh, dw, prescale, dw_prescale)
         ctx.shape = hidden.shape
         return rows.sum() / denom
 
     @staticmethod
     def backward(ctx, dloss):
-        dh, dw = ctx.saved_tensors
+        dh, dw, prescale, dw_prescale = ctx.saved_tensors
         scale = dloss.float()
+        if prescale is not None:
+            gh = _mul_fp32_scalar(dh, scale / prescale).view(ctx.shape) if dh is not None else None
+            gw = _mul_fp32_scalar(dw, scale / dw_prescale) if dw is not None else None
+            return gh, gw, None, None, None, None, None, None
         gh = torch.mul(dh, scale).view(ctx.shape) if dh is not None else None
         gw = torch.mul(dw, scale) if dw is not None else None
         return gh, gw, None, None, None, None, None, None
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """2^e as fp32 for an integer tensor e in [-126, 127], built in the exponent field: exact, where
+    ``torch.ldexp`` on the device goes through ``pow`` (measured: ldexp(1, 16) = 65535.996)."""
+    return torch.bitwise_left_shift(e.to(torch.int32) + 127, 23).view(torch.float32)
+
+
+def _mul_fp32_scalar(t: torch.Tensor, s: torch.Tensor, chunk: int = 1 << 24) -> torch.Tensor:
+    """``t * s`` for a contiguous fp16 ``t`` and an fp32 device scalar ``s``, the fp32 product rounded
+    once. ``torch.mul(t, s)`` casts ``s`` to fp16 first: 2^16 becomes inf (and 0 x inf a nan), 1/3 loses
+    13 bits. The fp32 product goes through ``chunk``-element pieces (64 MB), not a copy of ``t``."""
+    out = torch.empty_like(t)
+    src, dst = t.view(-1), out.view(-1)
+    for i in range(0, src.numel(), chunk):
+        dst[i:i + chunk].copy_(src[i:i + chunk].float().mul_(s))
+    return out
 
 
 def fused_lm_head_loss(hidden, lm_head: nn.Linear, labels, num_items_in_batch=None, ignore_index=-100,

@@ -118,6 +118,38 @@ def test_validation_errors_without_gpu():
         assert lib.smt_attn_fwd(ctypes.byref(t), ctypes.byref(t), ctypes.byref(t), ctypes.byref(t), tab,
                                 ctypes.byref(shape), None) == -1
         assert b"not a 16-bit format" in lib.smt_attn_last_error()
+    # ... an empty input included: rows / n = 0 is a no-op for a 16-bit dtype and an error for any other
+    # (the dtype is validated before the early return)
+    rt = _hip.RopeTensor(16, 16, 0, 0, 0, 0, 0, 0, 8, 0)
+    empty = {
+        "smt_ce_fwd": lambda dt: lib.smt_ce_fwd(None, 8, None, 0, 8, -100, None, None, dt, None),
+        "smt_ce_bwd": lambda dt: lib.smt_ce_bwd(None, 8, None, None, None, 0, 8, -100, None, 8, dt, None),
+        "smt_rmsnorm_fwd": lambda dt: lib.smt_rmsnorm_fwd(None, 512, None, None, 512, None, 0, 512, 1e-5, dt, None),
+        "smt_add_rmsnorm_fwd": lambda dt: lib.smt_add_rmsnorm_fwd(None, 512, None, 512, None, None, 512, None, 512, None,
+                                                                  0, 512, 1e-5, dt, None),
+        "smt_rmsnorm_bwd_add": lambda dt: lib.smt_rmsnorm_bwd_add(None, 512, None, 512, None, None, None, 512, None, 512,
+                                                                  0, 512, dt, None),
+        "smt_rmsnorm_bwd": lambda dt: lib.smt_rmsnorm_bwd(None, 512, None, 512, None, None, None, 512, None, None, 0, 512,
+                                                          dt, None),
+        "smt_rmsnorm_bwd_add_dw": lambda dt: lib.smt_rmsnorm_bwd_add_dw(None, 512, None, 512, None, None, None, 512, None,
+                                                                        512, None, None, 0, 512, dt, None),
+        "smt_rope_fwd": lambda dt: lib.smt_rope_fwd(ctypes.byref(rt), ctypes.byref(rt), tab, tab, 0, 128, 0, 16, 128, dt,
+                                                    None),
+        "smt_rope_bwd": lambda dt: lib.smt_rope_bwd(ctypes.byref(rt), ctypes.byref(rt), tab, tab, 0, 128, 0, 16, 128, dt,
+                                                    None),
+        "smt_swiglu_fwd": lambda dt: lib.smt_swiglu_fwd(None, None, None, 0, dt, None),
+        "smt_swiglu_bwd": lambda dt: lib.smt_swiglu_bwd(None, None, None, None, None, 0, dt, None),
+        "smt_colblock_recompute": lambda dt: lib.smt_colblock_recompute(0, None, 0, None, 0, None, None, 0, None, 1, None,
+                                                                        dt, None),
+    }
+    for name, call in empty.items():
+        for bad in (_hip.DTYPE_FP32, 7):
+            assert call(bad) == -1, (name, bad)
+            err = lib.smt_model_ops_last_error()
+            who = b"smt_rope" if "rope" in name else name.encode()
+            assert err.startswith(who + b": dtype") and b"not a 16-bit format" in err, (name, err)
+        for good in (_hip.DTYPE_BF16, _hip.DTYPE_FP16):
+            assert call(good) == 0, (name, good, lib.smt_model_ops_last_error())
     # channel path (ABI v3)
     assert lib.smt_row_gather(None, 256, 2, 256, None, 4, None, 256, None) == -1
     assert lib.smt_row_gather(None, 256, 2, 256, None, 0, None, 256, None) == 0       # no rows: no-op
