@@ -73,6 +73,51 @@ int smt_attn_bwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const
                        const uint64_t* key_mask, int64_t key_mask_ld, const smt_attn_shape* shape,
                        hipStream_t stream);
 
+/*
+ * Attention dropout (additive entry points; the ABI version is unchanged). The probabilities are
+ * dropped after the softmax: o = (softmax(...) o M) r v, with M the keep mask and r = 1 / (1 - p_eff).
+ * lse is that of the undropped probabilities; a row whose visible keys were all dropped gets o = 0 and
+ * a finite lse. The backward applies the same M: dS = P o (M o dP r - delta), dV = (P o M r)^T dO.
+ *
+ * The keep function is part of the contract. Whether probability (b, h, q, key) survives is a pure
+ * function of a 64-bit seed (seed_lo / seed_hi its halves) and those four indices, on uint32 with
+ * wrap-around -- never of S, the key mask, the dtype, the strides or which kernel asks:
+ *
+ *   mix(x):   x ^= x >> 16; x *= 0x21F0AAAD; x ^= x >> 15; x *= 0x735A2D97; x ^= x >> 15
+ *   head_key = mix(seed_lo + (b*Hq + h) * 0x9E3779B9) ^ seed_hi
+ *   row_key  = mix(head_key + q * 0x85EBCA6B)
+ *   word     = mix(row_key ^ ((key >> 2) * 0x9E3779B1))
+ *   byte     = (word >> (8 * (key & 3))) & 0xFF
+ *   keep     = byte >= t            with t = clamp(floor(p*256 + 0.5), 0, 255)
+ *
+ * The effective drop rate is p_eff = t / 256 and kept probabilities are scaled by 1 / (1 - p_eff).
+ * t == 0 is no dropout: the calls forward to smt_attn_fwd_kmask / smt_attn_bwd_kmask and seed may be
+ * NULL. seed: one uint64 in device memory, read by the kernels (no host synchronisation; a graph
+ * replay or a recompute that passes the same buffer sees the same masks). The masks are not torch's
+ * Philox stream: a run is not mask-for-mask comparable with torch's dropout.
+ *
+ * p outside [0, 1) or NaN, and a NULL seed with t > 0, return -1 before any HIP call.
+ */
+int smt_attn_dropout_threshold(float p);      /* t as above, or -1 for p outside [0, 1) or NaN */
+
+int smt_attn_fwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                         const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
+                         float p, const uint64_t* seed, const smt_attn_shape* shape, hipStream_t stream);
+int smt_attn_bwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                         const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
+                         const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
+                         const uint64_t* key_mask, int64_t key_mask_ld, float p, const uint64_t* seed,
+                         const smt_attn_shape* shape, hipStream_t stream);
+
+/*
+ * The keep mask itself: keep[((b*Hq + h)*S + q)*S + key] = 1 (kept) or 0 (dropped) for every
+ * (b, h, q, key) of a device uint8 [B][Hq][S][S] buffer, from the same device function the three
+ * kernels call (only B, Hq and S of the shape are used). A test oracle's input and a debugging aid,
+ * not part of the training path.
+ */
+int smt_attn_dropout_mask(uint8_t* keep, float p, const uint64_t* seed, const smt_attn_shape* shape,
+                          hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

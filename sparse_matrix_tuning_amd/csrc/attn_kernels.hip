@@ -1,5 +1,6 @@
 // Causal grouped-query flash attention for gfx950 (CDNA4), head_dim 128, bf16 or fp16 I/O (the model's
-// dtype, smt_attn_shape.dtype; ABI v13), fp32 softmax.
+// dtype, smt_attn_shape.dtype; ABI v13), fp32 softmax, optional attention dropout inside the three
+// kernels (DROP instances, smt_attn_*_dropout).
 // C ABI: include/smt_attention.h. Replaces transformers' sdpa attention (aotriton on this torch
 // build) in the LLaMA decoder that carries the SMT modules.
 //
@@ -268,6 +269,34 @@ constexpr int kTileB = kKV * kRowB;        // 16 KiB per operand tile
 // visible key is masked gets a zero output, lse = +inf and zero gradients (torch's safe softmax).
 __device__ __forceinline__ bool key_bit(uint64_t w, int key) { return (w >> (key & 63)) & 1ull; }
 
+// Attention dropout (DROP instances, smt_attn_*_dropout; the keep function is documented in
+// include/smt_attention.h and is part of the contract). One 32-bit word decides 4 consecutive keys of
+// one query row, one byte each: keep = byte >= t. The forward and dQ lanes hold one q and runs of 4
+// consecutive keys (one drop_word per 4 elements, row_key once per lane); a dK/dV lane holds one key
+// and 16 rows per slice (DkvLean: the slice's 32 row keys once per workgroup, each word once per
+// 4-lane group). The export kernel and the three attention kernels call these same functions.
+struct DropArgs {
+    const uint64_t* seed;                  // one value in device memory
+    uint32_t t;                            // threshold, 1..255
+    float r;                               // 1 / (1 - t/256)
+};
+__device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
+    x ^= x >> 16; x *= 0x21F0AAADu; x ^= x >> 15; x *= 0x735A2D97u; x ^= x >> 15;
+    return x;
+}
+__device__ __forceinline__ uint32_t drop_head_key(uint64_t seed, uint32_t bh) {       // bh = b*Hq + h
+    return drop_mix((uint32_t)seed + bh * 0x9E3779B9u) ^ (uint32_t)(seed >> 32);
+}
+__device__ __forceinline__ uint32_t drop_row_key(uint32_t head_key, uint32_t q) {
+    return drop_mix(head_key + q * 0x85EBCA6Bu);
+}
+constexpr uint32_t kDropKeyMul = 0x9E3779B1u;
+// key_term = (key >> 2) * kDropKeyMul (callers with compile-time key offsets add their multiples)
+__device__ __forceinline__ uint32_t drop_word(uint32_t row_key, uint32_t key_term) { return drop_mix(row_key ^ key_term); }
+__device__ __forceinline__ bool drop_keep(uint32_t word, uint32_t key_lo2, uint32_t t) {
+    return ((word >> (8u * key_lo2)) & 0xFFu) >= t;
+}
+
 struct FwdArgs {
     Tns q, k, v;
     uint16_t* o;
@@ -277,6 +306,7 @@ struct FwdArgs {
     int64_t kmask_ld;
     int B, Hq, Hkv, S;
     float sl2;                             // scale * log2(e)
+    DropArgs drop;                         // read by the DROP instances only
 };
 
 // Causal balance: a workgroup takes the query blocks qb and nqb-1-qb (equal total work per workgroup).
@@ -321,7 +351,7 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
 // one wave per SIMD over 64 rows (two builds), all slower.
 // ------------------------------------------------------------------------------------------------
 
-template <bool KMASK, int F>
+template <bool KMASK, int F, bool DROP>
 struct FwdLean {
     const FwdArgs& a;
     uint8_t* lds;
@@ -332,6 +362,7 @@ struct FwdLean {
     f32x16_t o[4];
     float m_run, l_run;
     int qw, qrow, hi, l32, wave, lane, nt, last;
+    uint32_t drop_rk;                      // DROP: the lane's row key
     TrLane tl;
 
     __device__ __forceinline__ FwdLean(const FwdArgs& a_, uint8_t* lds_) : a(a_), lds(lds_) {}
@@ -427,6 +458,18 @@ struct FwdLean {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
         }
+        if constexpr (DROP) {
+            // only the P tile of the PV product is dropped: the running max and sum above are those
+            // of the undropped probabilities (r folds into the final 1 / l)
+            const uint32_t kt0 = ((uint32_t)(k0 >> 2) + (uint32_t)hi) * kDropKeyMul;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {                      // keys k0 + 32 (w>>2) + 8 (w&3) + 4 hi + 0..3
+                const uint32_t word = drop_word(drop_rk, kt0 + (uint32_t)(8 * (w >> 2) + 2 * (w & 3)) * kDropKeyMul);
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (!drop_keep(word, c, a.drop.t)) x[4 * w + c] = 0.f;
+            }
+        }
         bf16x8_t pf[4];
         pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[0]), pf[0], pf[1]);
         pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[16]), pf[2], pf[3]);
@@ -462,6 +505,7 @@ struct FwdLean {
         const uint16_t* kp = a.k.p + b * a.k.sb + hk * a.k.sh;
         const uint16_t* vp = a.v.p + b * a.v.sb + hk * a.v.sh;
         km = KMASK ? a.kmask + (int64_t)b * a.kmask_ld : nullptr;
+        if constexpr (DROP) drop_rk = drop_row_key(drop_head_key(*a.drop.seed, (uint32_t)(b * a.Hq + h)), (uint32_t)qrow);
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             if (qrow < a.S) qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + qrow * a.q.ss + 16 * ks + 8 * hi);
@@ -490,7 +534,8 @@ struct FwdLean {
         }
         const float l_tot = halves_sum(l_run);
         if (qrow < a.S) {
-            const float inv = (KMASK && !(l_tot > 0.f)) ? 0.f : 1.f / l_tot;
+            float inv = (KMASK && !(l_tot > 0.f)) ? 0.f : 1.f / l_tot;
+            if constexpr (DROP) inv *= a.drop.r;
             uint16_t* op = a.o + b * a.o_sb + h * a.o_sh + (int64_t)qrow * a.o_ss;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
@@ -509,7 +554,7 @@ struct FwdLean {
     }
 };
 
-template <bool KMASK, int F>
+template <bool KMASK, int F, bool DROP>
 __global__ __launch_bounds__(64 * kFwdWaves, 2)
 void attn_fwd_kernel(FwdArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // K/V ring: 2 x 32 KiB
@@ -523,7 +568,7 @@ void attn_fwd_kernel(FwdArgs a) {
     const int grp = L / per_group;
     const int rem = L - grp * per_group;
     const int hk = grp % a.Hkv;
-    FwdLean<KMASK, F> fl(a, lds);
+    FwdLean<KMASK, F, DROP> fl(a, lds);
     fl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
 }
 
@@ -545,6 +590,7 @@ struct DqArgs {
     int64_t kmask_ld;
     int B, Hq, Hkv, S;
     float sl2, scale;
+    DropArgs drop;                         // read by the DROP instances only
 };
 
 // dQ (DqLean): a workgroup = 4 waves x 32 query rows of one (b, q head) sweeping the K/V tiles up to
@@ -553,7 +599,7 @@ struct DqArgs {
 // fp32, the causal test only on the wave's diagonal tile, scheduling fences that bound the fragment
 // reads hoisted ahead. Measured and removed (git history): one wave per SIMD with AGPR
 // accumulators, and dQ as a GEMM over a materialised dS, both slower.
-template <bool KMASK, int F>
+template <bool KMASK, int F, bool DROP>
 struct DqLean {
     const DqArgs& a;
     uint8_t* lds;
@@ -563,6 +609,7 @@ struct DqLean {
     const uint64_t* km;
     __amdgpu_buffer_rsrc_t rk, rv;
     uint32_t lds0, lo_row, lo_t0, lo_t4;
+    uint32_t drop_rk;                      // DROP: the lane's row key
     int lane, wave, hi, l32, qw, qrow, nt, last;
 
     __device__ __forceinline__ DqLean(const DqArgs& a_, uint8_t* lds_) : a(a_), lds(lds_) {}
@@ -619,6 +666,16 @@ struct DqLean {
                 }
             }
         }
+        if constexpr (DROP) {                                  // dS = P (M dP r - delta)
+            const uint32_t kt0 = ((uint32_t)(k0 >> 2) + (uint32_t)hi) * kDropKeyMul;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {                      // keys k0 + 32 (w>>2) + 8 (w&3) + 4 hi + 0..3
+                const uint32_t word = drop_word(drop_rk, kt0 + (uint32_t)(8 * (w >> 2) + 2 * (w & 3)) * kDropKeyMul);
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    dp[w >> 2][4 * (w & 3) + c] = drop_keep(word, c, a.drop.t) ? dp[w >> 2][4 * (w & 3) + c] * a.drop.r : 0.f;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 32; i += 2) {
             const int j = i >> 4, ii = i & 15;
@@ -661,6 +718,7 @@ struct DqLean {
         const uint16_t* kp = a.k.p + b * a.k.sb + hk * a.k.sh;
         const uint16_t* vp = a.v.p + b * a.v.sb + hk * a.v.sh;
         km = KMASK ? a.kmask + (int64_t)b * a.kmask_ld : nullptr;
+        if constexpr (DROP) drop_rk = drop_row_key(drop_head_key(*a.drop.seed, (uint32_t)(b * a.Hq + h)), (uint32_t)qrow);
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             if (qvalid) {
@@ -731,7 +789,7 @@ struct DqLean {
     }
 };
 
-template <bool KMASK, int F>
+template <bool KMASK, int F, bool DROP>
 __global__ __launch_bounds__(64 * kDqWaves, 8 / kDqWaves)
 void attn_dq_kernel(DqArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // 64 KiB
@@ -745,7 +803,7 @@ void attn_dq_kernel(DqArgs a) {
     const int grp = L / per_group;
     const int rem = L - grp * per_group;
     const int hk = grp % a.Hkv;
-    DqLean<KMASK, F> dl(a, lds);
+    DqLean<KMASK, F, DROP> dl(a, lds);
     dl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
 }
 
@@ -781,6 +839,7 @@ struct DkvArgs {
     int64_t kmask_ld;
     int B, Hq, Hkv, S;
     float sl2, scale;
+    DropArgs drop;                         // read by the DROP instances only
 };
 
 // dK / dV (DkvLean): the slice loop unrolled by two so that the ring slot is a compile-time LDS offset (the ring now sits in front of the V
@@ -795,7 +854,16 @@ struct DkvArgs {
 // measured 2.17, 2.21, 2.21 ms for the whole backward: profiles/r03_attn_bwd_variants.jsonl)
 constexpr int kDkvLeanRing = 2;
 static_assert(kDkvLeanRing >= 2 && kDkvLeanRing * kSliceBuf + kVImg <= 160 * 1024, "dK/dV lean ring");
-template <bool KMASK, int F>
+// DROP: the 32 row keys of each ring slot's slice (one workgroup-wide copy, written by issue() under the
+// ring's own barriers), after the V image so that the other LDS offsets are those of the plain kernels
+constexpr int kDropRkOff = kDkvLeanRing * kSliceBuf + kVImg, kDropRkB = kSlice * 4;
+static_assert(kDropRkOff + kDkvLeanRing * kDropRkB <= 160 * 1024, "dK/dV row keys");
+// the word of 4-lane group member c, for all 4 lanes of the group (v_mov_b32 quad_perm:[c,c,c,c])
+template <int C>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, C * 0x55, 0xf, 0xf, true);
+}
+template <bool KMASK, int F, bool DROP>
 struct DkvLean {
     const DkvArgs& a;
     uint8_t* lds;
@@ -805,6 +873,8 @@ struct DkvLean {
     bool kvalid;
     uint32_t lds0;
     uint32_t lo_row, lo_v, lo_t0, lo_t4;      // lane constants of the row / V-row / transposed reads
+    uint64_t drop_seed;                       // DROP: the seed, the lane's (key >> 2) term and key & 3
+    uint32_t drop_kt, drop_klo;
 
     __device__ __forceinline__ DkvLean(const DkvArgs& a_, uint8_t* lds_) : a(a_), lds(lds_) {}
 
@@ -830,6 +900,12 @@ struct DkvLean {
             const float* row = (wave == 0 ? a.lse : a.delta) + ((int64_t)b * a.Hq + h) * a.S;
             dma16(uniform_rsrc(row, (int64_t)a.S * 4), __builtin_amdgcn_readfirstlane(buf + 2 * kSliceB + 128 * wave),
                   (s0 + 4 * lane) * 4);
+        }
+        if constexpr (DROP) {
+            if (wave == 2 && lane < kSlice) {
+                uint32_t* rkeys = reinterpret_cast<uint32_t*>(lds + kDropRkOff + (it % kDkvLeanRing) * kDropRkB);
+                rkeys[lane] = drop_row_key(drop_head_key(drop_seed, (uint32_t)(b * a.Hq + h)), (uint32_t)(s0 + lane));
+            }
         }
     }
 
@@ -887,6 +963,20 @@ struct DkvLean {
 #pragma unroll
             for (int i = 0; i < 16; ++i) pr[i] = 0.f;
         }
+        bool kp[16];                                       // DROP: element i is kept
+        if constexpr (DROP) {
+            // the lane's 16 rows x its key need 16 words, the same 16 for the 4 lanes that share
+            // key >> 2: member c of the group hashes the rows with (i & 3) == c, and all four read them
+            const uint32_t* rkeys = reinterpret_cast<const uint32_t*>(lds + kDropRkOff + SLOT * kDropRkB);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t wq = drop_word(rkeys[8 * g + 4 * hi + (lane & 3)], drop_kt);
+                kp[4 * g + 0] = drop_keep(quad_bcast<0>(wq), drop_klo, a.drop.t);
+                kp[4 * g + 1] = drop_keep(quad_bcast<1>(wq), drop_klo, a.drop.t);
+                kp[4 * g + 2] = drop_keep(quad_bcast<2>(wq), drop_klo, a.drop.t);
+                kp[4 * g + 3] = drop_keep(quad_bcast<3>(wq), drop_klo, a.drop.t);
+            }
+        }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const float4 dz = *reinterpret_cast<const float4*>(cst + 32 + 8 * g + 4 * hi);
@@ -894,10 +984,17 @@ struct DkvLean {
             for (int h = 0; h < 2; ++h) {
                 const int i = 4 * g + 2 * h;
                 const f32x2_t d2 = h ? f32x2_t{dz.z, dz.w} : f32x2_t{dz.x, dz.y};
-                const f32x2_t r = submul2<kPkDkv>(f32x2_t{dp[i], dp[i + 1]}, d2, f32x2_t{pr[i], pr[i + 1]});
+                f32x2_t dpv = {dp[i], dp[i + 1]};
+                if constexpr (DROP)                        // dS = P (M dP r - delta)
+                    dpv = f32x2_t{kp[i] ? dp[i] * a.drop.r : 0.f, kp[i + 1] ? dp[i + 1] * a.drop.r : 0.f};
+                const f32x2_t r = submul2<kPkDkv>(dpv, d2, f32x2_t{pr[i], pr[i + 1]});
                 dsv[i] = r.x;
                 dsv[i + 1] = r.y;
             }
+        }
+        if constexpr (DROP) {                              // dV^T += dO^T (P M); r at the end (run)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) pr[i] = kp[i] ? pr[i] : 0.f;
         }
         bf16x8_t pf[2], sf[2];
         pack_b_frags<F>(pr, pf[0], pf[1]);
@@ -953,6 +1050,11 @@ struct DkvLean {
         kw = k0 + wave * kKW;
         key = kw + l32;
         kvalid = !KMASK || (key < a.S && key_bit(a.kmask[(int64_t)b * a.kmask_ld + (key >> 6)], key));
+        if constexpr (DROP) {
+            drop_seed = *a.drop.seed;
+            drop_kt = (uint32_t)(key >> 2) * kDropKeyMul;
+            drop_klo = (uint32_t)(key & 3);
+        }
         const uint16_t* kp = a.k.p + b * a.k.sb + hk * a.k.sh;
         const uint16_t* vp = a.v.p + b * a.v.sb + hk * a.v.sh;
         lds0 = lds_addr(lds);
@@ -985,6 +1087,12 @@ struct DkvLean {
         vm_wait_all_known();                               // the K fragments too (compiler-visible)
         __syncthreads();
         for (int it = 0; it < n_it; it += kDkvLeanRing) steps<0>(it);
+        if constexpr (DROP) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) dvt[dt][i] *= a.drop.r;
+        }
         if (key < a.S) {
             uint16_t* dkr = a.dk + b * a.dk_sb + hk * a.dk_sh + (int64_t)key * a.dk_ss;
             uint16_t* dvr = a.dv + b * a.dv_sb + hk * a.dv_sh + (int64_t)key * a.dv_ss;
@@ -1005,10 +1113,10 @@ struct DkvLean {
     }
 };
 
-template <bool KMASK, int F>
+template <bool KMASK, int F, bool DROP>
 __global__ __launch_bounds__(kDkvWaves * 64, 2)
 void attn_dkdv_kernel(DkvArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kVImg + kDkvLeanRing * kSliceBuf];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kVImg + kDkvLeanRing * (kSliceBuf + (DROP ? kDropRkB : 0))];
     const int nkb = (a.S + kKB - 1) / kKB;
     const int total = ((nkb + 1) / 2) * a.Hkv * a.B;
     // key blocks kb (long causal sweep) and nkb-1-kb (short) in one workgroup: equal work per
@@ -1017,8 +1125,24 @@ void attn_dkdv_kernel(DkvArgs a) {
 #pragma nounroll
     for (int i = 0; i < t.n; ++i) {
         if (i) __syncthreads();
-        DkvLean<KMASK, F> dl(a, lds);
+        DkvLean<KMASK, F, DROP> dl(a, lds);
         dl.run(t.b, t.hk, t.blk[1 - i]);
+    }
+}
+
+// The keep mask of every (b, h, q, key) as bytes (smt_attn_dropout_mask): one thread per 4-key word.
+__global__ __launch_bounds__(256)
+void attn_dropout_mask_kernel(uint8_t* keep, DropArgs drop, int S, int64_t n_words) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_words) return;
+    const int wpr = (S + 3) >> 2;                          // words per (b, h, q) row
+    const int64_t row = i / wpr;                           // (b*Hq + h)*S + q
+    const int kw = (int)(i - row * wpr);
+    const uint32_t bh = (uint32_t)(row / S), q = (uint32_t)(row - (int64_t)bh * S);
+    const uint32_t word = drop_word(drop_row_key(drop_head_key(*drop.seed, bh), q), (uint32_t)kw * kDropKeyMul);
+    for (int c = 0; c < 4; ++c) {
+        const int key = 4 * kw + c;
+        if (key < S) keep[row * S + key] = drop_keep(word, (uint32_t)c, drop.t) ? 1 : 0;
     }
 }
 
@@ -1041,32 +1165,48 @@ int check_shape(const smt_attn_shape* s, const char* fn) {
     return 0;
 }
 
-// the (key mask, format) instance of a kernel template
-#define SMT_ATTN_LAUNCH(kernel, kmask, dtype, grid, block, stream, args)                                         \
+// the (key mask, format, dropout) instance of a kernel template
+#define SMT_ATTN_LAUNCH_KD(kernel, F, kmask, drop, grid, block, stream, args)                                    \
     do {                                                                                                      \
-        if ((dtype) == SMT_DTYPE_FP16) {                                                                      \
-            if (kmask) hipLaunchKernelGGL((kernel<true, SMT_DTYPE_FP16>), grid, block, 0, stream, args);     \
-            else hipLaunchKernelGGL((kernel<false, SMT_DTYPE_FP16>), grid, block, 0, stream, args);          \
+        if (drop) {                                                                                           \
+            if (kmask) hipLaunchKernelGGL((kernel<true, F, true>), grid, block, 0, stream, args);            \
+            else hipLaunchKernelGGL((kernel<false, F, true>), grid, block, 0, stream, args);                 \
         } else {                                                                                              \
-            if (kmask) hipLaunchKernelGGL((kernel<true, SMT_DTYPE_BF16>), grid, block, 0, stream, args);     \
-            else hipLaunchKernelGGL((kernel<false, SMT_DTYPE_BF16>), grid, block, 0, stream, args);          \
+            if (kmask) hipLaunchKernelGGL((kernel<true, F, false>), grid, block, 0, stream, args);           \
+            else hipLaunchKernelGGL((kernel<false, F, false>), grid, block, 0, stream, args);                \
         }                                                                                                     \
+    } while (0)
+#define SMT_ATTN_LAUNCH(kernel, kmask, dtype, drop, grid, block, stream, args)                                   \
+    do {                                                                                                      \
+        if ((dtype) == SMT_DTYPE_FP16) SMT_ATTN_LAUNCH_KD(kernel, SMT_DTYPE_FP16, kmask, drop, grid, block, stream, args); \
+        else SMT_ATTN_LAUNCH_KD(kernel, SMT_DTYPE_BF16, kmask, drop, grid, block, stream, args);             \
     } while (0)
 
 Tns tns(const smt_attn_tensor* t) { return Tns{static_cast<const uint16_t*>(t->ptr), t->sb, t->sh, t->ss}; }
 
-}  // namespace
+// t of the keep function, or -1 for p outside [0, 1) or NaN
+int drop_threshold(float p) {
+    if (!(p >= 0.f && p < 1.f)) return -1;
+    const int t = (int)(p * 256.f + 0.5f);
+    return t > 255 ? 255 : t;
+}
 
-extern "C" {
+// p and seed of a *_dropout call -> DropArgs (t == 0: no dropout); validated before any HIP call
+int check_drop(float p, const uint64_t* seed, const char* fn, DropArgs* d) {
+    const int t = drop_threshold(p);
+    if (t < 0) return fail(-1, "%s: dropout p = %g is outside [0, 1)", fn, (double)p);
+    if (t > 0 && !seed) return fail(-1, "%s: null seed with dropout p = %g", fn, (double)p);
+    d->seed = seed;
+    d->t = (uint32_t)t;
+    d->r = 256.f / (float)(256 - t);
+    return 0;
+}
 
-const char* smt_attn_last_error(void) { return g_err; }
-
-
-int smt_attn_fwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
-                       const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
-                       const smt_attn_shape* shape, hipStream_t stream) {
+// fn: the entry point's name for messages; drop.t == 0: the plain kernels
+int attn_fwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+             const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld, DropArgs drop,
+             const smt_attn_shape* shape, hipStream_t stream) {
     int rc;
-    const char* fn = key_mask ? "smt_attn_fwd_kmask" : "smt_attn_fwd";
     if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
         (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)))
         return rc;
@@ -1080,11 +1220,73 @@ int smt_attn_fwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const
     a.kmask = key_mask; a.kmask_ld = key_mask_ld;
     a.B = shape->B; a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.S = shape->S;
     a.sl2 = shape->scale * 1.4426950408889634f;
+    a.drop = drop;
     const int64_t nqb = (shape->S + kFwdQB - 1) / kFwdQB;
     const int64_t blocks = nqb * shape->Hq * shape->B;
     if (blocks > 0x7fffffffLL) return fail(-1, "%s: too many blocks", fn);
-    SMT_ATTN_LAUNCH(attn_fwd_kernel, key_mask, shape->dtype, dim3((unsigned)blocks), dim3(64 * kFwdWaves), stream, a);
+    SMT_ATTN_LAUNCH(attn_fwd_kernel, key_mask, shape->dtype, drop.t != 0, dim3((unsigned)blocks), dim3(64 * kFwdWaves),
+                    stream, a);
     return check_launch("attn_fwd_kernel");
+}
+
+int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+             const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
+             const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
+             const uint64_t* key_mask, int64_t key_mask_ld, DropArgs drop, const smt_attn_shape* shape,
+             hipStream_t stream) {
+    int rc;
+    if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
+        (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)) || (rc = check_tensor(d_o, "do", fn)) ||
+        (rc = check_tensor(dq, "dq", fn)) || (rc = check_tensor(dk, "dk", fn)) || (rc = check_tensor(dv, "dv", fn)))
+        return rc;
+    if (!lse || !delta_ws) return fail(-1, "%s: null lse / delta workspace", fn);
+    if (!al16(lse) || !al16(delta_ws) || (shape->S & 3)) return fail(-2, "%s: lse / delta need 16-byte rows (S %% 4 == 0)", fn);
+    if (key_mask && key_mask_ld < (shape->S + 63) / 64)
+        return fail(-1, "%s: key_mask_ld %lld < ceil(S / 64)", fn, (long long)key_mask_ld);
+    const int B = shape->B, Hq = shape->Hq, Hkv = shape->Hkv, S = shape->S;
+    const float sl2 = shape->scale * 1.4426950408889634f;
+    const bool dropping = drop.t != 0;
+
+    DqArgs qa;
+    qa.q = tns(q); qa.k = tns(k); qa.v = tns(v); qa.dout = tns(d_o); qa.o = tns(o);
+    qa.dq = static_cast<uint16_t*>(dq->ptr); qa.dq_sb = dq->sb; qa.dq_sh = dq->sh; qa.dq_ss = dq->ss;
+    qa.lse = lse; qa.delta = delta_ws;
+    qa.kmask = key_mask; qa.kmask_ld = key_mask_ld;
+    qa.B = B; qa.Hq = Hq; qa.Hkv = Hkv; qa.S = S; qa.sl2 = sl2; qa.scale = shape->scale;
+    qa.drop = drop;
+    const int64_t nqb = (S + kDqQB - 1) / kDqQB;
+    const dim3 qgrid((unsigned)(nqb * Hq * B)), qblock(64 * kDqWaves);
+    SMT_ATTN_LAUNCH(attn_dq_kernel, key_mask, shape->dtype, dropping, qgrid, qblock, stream, qa);
+    if ((rc = check_launch("attn_dq_kernel"))) return rc;
+
+    DkvArgs ka;
+    ka.q = tns(q); ka.k = tns(k); ka.v = tns(v); ka.dout = tns(d_o);
+    ka.dk = static_cast<uint16_t*>(dk->ptr); ka.dk_sb = dk->sb; ka.dk_sh = dk->sh; ka.dk_ss = dk->ss;
+    ka.dv = static_cast<uint16_t*>(dv->ptr); ka.dv_sb = dv->sb; ka.dv_sh = dv->sh; ka.dv_ss = dv->ss;
+    ka.lse = lse; ka.delta = delta_ws;
+    ka.kmask = key_mask; ka.kmask_ld = key_mask_ld;
+    ka.B = B; ka.Hq = Hq; ka.Hkv = Hkv; ka.S = S; ka.sl2 = sl2; ka.scale = shape->scale;
+    ka.drop = drop;
+    const int64_t nkb = (S + kKB - 1) / kKB;
+    const dim3 grid((unsigned)(((nkb + 1) / 2) * Hkv * B));
+    SMT_ATTN_LAUNCH(attn_dkdv_kernel, key_mask, shape->dtype, dropping, grid, dim3(kDkvWaves * 64), stream, ka);
+    return check_launch("attn_dkdv_kernel");
+}
+
+constexpr DropArgs kNoDrop = {nullptr, 0u, 1.f};
+
+}  // namespace
+
+extern "C" {
+
+const char* smt_attn_last_error(void) { return g_err; }
+
+
+int smt_attn_fwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                       const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
+                       const smt_attn_shape* shape, hipStream_t stream) {
+    return attn_fwd(key_mask ? "smt_attn_fwd_kmask" : "smt_attn_fwd", q, k, v, o, lse, key_mask, key_mask_ld, kNoDrop,
+                    shape, stream);
 }
 
 int smt_attn_fwd(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1097,41 +1299,8 @@ int smt_attn_bwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const
                        const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
                        const uint64_t* key_mask, int64_t key_mask_ld, const smt_attn_shape* shape,
                        hipStream_t stream) {
-    int rc;
-    const char* fn = key_mask ? "smt_attn_bwd_kmask" : "smt_attn_bwd";
-    if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
-        (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)) || (rc = check_tensor(d_o, "do", fn)) ||
-        (rc = check_tensor(dq, "dq", fn)) || (rc = check_tensor(dk, "dk", fn)) || (rc = check_tensor(dv, "dv", fn)))
-        return rc;
-    if (!lse || !delta_ws) return fail(-1, "%s: null lse / delta workspace", fn);
-    if (!al16(lse) || !al16(delta_ws) || (shape->S & 3)) return fail(-2, "%s: lse / delta need 16-byte rows (S %% 4 == 0)", fn);
-    if (key_mask && key_mask_ld < (shape->S + 63) / 64)
-        return fail(-1, "%s: key_mask_ld %lld < ceil(S / 64)", fn, (long long)key_mask_ld);
-    const int B = shape->B, Hq = shape->Hq, Hkv = shape->Hkv, S = shape->S;
-    const float sl2 = shape->scale * 1.4426950408889634f;
-
-    DqArgs qa;
-    qa.q = tns(q); qa.k = tns(k); qa.v = tns(v); qa.dout = tns(d_o); qa.o = tns(o);
-    qa.dq = static_cast<uint16_t*>(dq->ptr); qa.dq_sb = dq->sb; qa.dq_sh = dq->sh; qa.dq_ss = dq->ss;
-    qa.lse = lse; qa.delta = delta_ws;
-    qa.kmask = key_mask; qa.kmask_ld = key_mask_ld;
-    qa.B = B; qa.Hq = Hq; qa.Hkv = Hkv; qa.S = S; qa.sl2 = sl2; qa.scale = shape->scale;
-    const int64_t nqb = (S + kDqQB - 1) / kDqQB;
-    const dim3 qgrid((unsigned)(nqb * Hq * B)), qblock(64 * kDqWaves);
-    SMT_ATTN_LAUNCH(attn_dq_kernel, key_mask, shape->dtype, qgrid, qblock, stream, qa);
-    if ((rc = check_launch("attn_dq_kernel"))) return rc;
-
-    DkvArgs ka;
-    ka.q = tns(q); ka.k = tns(k); ka.v = tns(v); ka.dout = tns(d_o);
-    ka.dk = static_cast<uint16_t*>(dk->ptr); ka.dk_sb = dk->sb; ka.dk_sh = dk->sh; ka.dk_ss = dk->ss;
-    ka.dv = static_cast<uint16_t*>(dv->ptr); ka.dv_sb = dv->sb; ka.dv_sh = dv->sh; ka.dv_ss = dv->ss;
-    ka.lse = lse; ka.delta = delta_ws;
-    ka.kmask = key_mask; ka.kmask_ld = key_mask_ld;
-    ka.B = B; ka.Hq = Hq; ka.Hkv = Hkv; ka.S = S; ka.sl2 = sl2; ka.scale = shape->scale;
-    const int64_t nkb = (S + kKB - 1) / kKB;
-    const dim3 grid((unsigned)(((nkb + 1) / 2) * Hkv * B));
-    SMT_ATTN_LAUNCH(attn_dkdv_kernel, key_mask, shape->dtype, grid, dim3(kDkvWaves * 64), stream, ka);
-    return check_launch("attn_dkdv_kernel");
+    return attn_bwd(key_mask ? "smt_attn_bwd_kmask" : "smt_attn_bwd", q, k, v, o, d_o, lse, delta_ws, dq, dk, dv,
+                    key_mask, key_mask_ld, kNoDrop, shape, stream);
 }
 
 int smt_attn_bwd(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1139,6 +1308,53 @@ int smt_attn_bwd(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_a
                  const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
                  const smt_attn_shape* shape, hipStream_t stream) {
     return smt_attn_bwd_kmask(q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, nullptr, 0, shape, stream);
+}
+
+int smt_attn_dropout_threshold(float p) { return drop_threshold(p); }
+
+int smt_attn_fwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                         const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
+                         float p, const uint64_t* seed, const smt_attn_shape* shape, hipStream_t stream) {
+    DropArgs drop;
+    int rc;
+    if ((rc = check_drop(p, seed, "smt_attn_fwd_dropout", &drop))) return rc;
+    if (drop.t == 0) return smt_attn_fwd_kmask(q, k, v, o, lse, key_mask, key_mask_ld, shape, stream);
+    return attn_fwd("smt_attn_fwd_dropout", q, k, v, o, lse, key_mask, key_mask_ld, drop, shape, stream);
+}
+
+int smt_attn_bwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                         const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
+                         const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
+                         const uint64_t* key_mask, int64_t key_mask_ld, float p, const uint64_t* seed,
+                         const smt_attn_shape* shape, hipStream_t stream) {
+    DropArgs drop;
+    int rc;
+    if ((rc = check_drop(p, seed, "smt_attn_bwd_dropout", &drop))) return rc;
+    if (drop.t == 0)
+        return smt_attn_bwd_kmask(q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, key_mask, key_mask_ld, shape, stream);
+    return attn_bwd("smt_attn_bwd_dropout", q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, key_mask, key_mask_ld, drop, shape,
+                    stream);
+}
+
+int smt_attn_dropout_mask(uint8_t* keep, float p, const uint64_t* seed, const smt_attn_shape* shape,
+                          hipStream_t stream) {
+    const char* fn = "smt_attn_dropout_mask";
+    DropArgs drop;
+    int rc;
+    if ((rc = check_drop(p, seed, fn, &drop)) || (rc = check_shape(shape, fn))) return rc;
+    if (!keep) return fail(-1, "%s: null keep buffer", fn);
+    const int64_t rows = (int64_t)shape->B * shape->Hq * shape->S;
+    if (rows > 0xffffffffLL) return fail(-1, "%s: B * Hq * S must stay below 2^32", fn);
+    if (drop.t == 0) {                                     // no dropout: every element is kept
+        if (hipMemsetAsync(keep, 1, (size_t)rows * shape->S, stream) != hipSuccess)
+            return fail(-4, "%s: hipMemsetAsync failed", fn);
+        return 0;
+    }
+    const int64_t n_words = rows * ((shape->S + 3) / 4);
+    const int64_t blocks = (n_words + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail(-1, "%s: too many blocks", fn);
+    hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, keep, drop, shape->S, n_words);
+    return check_launch("attn_dropout_mask_kernel");
 }
 
 }  // extern "C"

@@ -775,13 +775,63 @@ class KeyMask:
         return cls(bits.contiguous(), S)
 
 
+def dropout_threshold(p: float) -> int:
+    """The 8-bit threshold ``t`` of the attention-dropout keep function (include/smt_attention.h):
+    ``clamp(floor(p * 256 + 0.5), 0, 255)``; ``p`` outside [0, 1) raises."""
+    t = _hip.load().smt_attn_dropout_threshold(float(p))
+    if t < 0:
+        raise ValueError(f"flash attention: dropout p = {p} is outside [0, 1)")
+    return t
+
+
+def dropout_effective_p(p: float) -> float:
+    """The drop rate the kernels apply for ``dropout_p=p``: ``t / 256``. Kept probabilities are scaled
+    by ``1 / (1 - dropout_effective_p(p))``."""
+    return dropout_threshold(p) / 256.0
+
+
+def _seed_tensor(seed, device) -> torch.Tensor:
+    """The 64-bit dropout seed as a 1-element int64 device tensor (an int is taken modulo 2^64)."""
+    if seed is None:
+        raise ValueError("flash attention: a dropout seed is needed (an int or a 1-element int64 device tensor)")
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != device:
+            raise ValueError("flash attention: seed must be an int or a 1-element int64 tensor on q's device")
+        return seed.reshape(1)
+    s = int(seed) & (2 ** 64 - 1)
+    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s], dtype=torch.int64, device=device)
+
+
+def flash_dropout_mask(B: int, Hq: int, S: int, p: float, seed, device) -> torch.Tensor:
+    """The keep mask the smt_flash kernels apply for (``p``, ``seed``): bool ``[B, Hq, S, S]``, element
+    (b, h, q, key) True = that probability is kept. Written by ``smt_attn_dropout_mask`` from the
+    kernels' own keep function (a test oracle's input and a debugging aid)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("flash_dropout_mask: a ROCm device is needed (the mask is written by a HIP kernel)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    t = dropout_threshold(p)
+    seed_t = _seed_tensor(seed, device) if t else None
+    keep = torch.empty(B, Hq, S, S, dtype=torch.uint8, device=device)
+    shape = _hip.AttnShape(B, Hq, Hq, S, 1.0, _hip.DTYPE_BF16)
+    with torch.cuda.device(device):
+        rc = _hip.load().smt_attn_dropout_mask(keep.data_ptr(), float(p), seed_t.data_ptr() if t else None,
+                                               ctypes.byref(shape), _stream(keep))
+    _hip._check(rc, "smt_attn_dropout_mask")
+    return keep.bool()
+
+
 class FlashAttnFn(torch.autograd.Function):
     """Causal GQA attention: q [B, Hq, S, 128], k / v [B, Hkv, S, 128] (any strides with head_dim
     innermost) -> o [B, S, Hq, 128] (the layout transformers' attention functions return).
-    ``key_mask``: optional :class:`KeyMask` (padded batches)."""
+    ``key_mask``: optional :class:`KeyMask` (padded batches). ``dropout_p``: attention dropout inside
+    the kernels (the keep function of include/smt_attention.h; effective rate
+    :func:`dropout_effective_p`); ``seed``: an int or a 1-element int64 device tensor, drawn from the
+    device generator when None (no host sync; ``torch.utils.checkpoint`` replays it)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, key_mask=None, joint=False):
+    def forward(ctx, q, k, v, scale, key_mask=None, joint=False, dropout_p=0.0, seed=None):
         for t, n in ((q, "q"), (k, "k"), (v, "v")):
             _need(t, "flash attention " + n, like=q)
         B, Hq, S, D = q.shape
@@ -803,18 +853,30 @@ class FlashAttnFn(torch.autograd.Function):
                 raise ValueError(f"flash attention: key mask for [{key_mask.bits.shape[0]}, {key_mask.S}] keys, "
                                  f"batch has [{B}, {S}]")
             km, km_ld = key_mask.bits.data_ptr(), key_mask.bits.shape[1]
-        rc = _hip.load().smt_attn_fwd_kmask(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
-                                            ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
-                                            lse.data_ptr(), km, km_ld, ctypes.byref(shape), _stream(q))
-        _hip._check(rc, "smt_attn_fwd")
-        ctx.save_for_backward(q, k, v, o, lse, key_mask.bits if key_mask is not None else None)
+        dropout_p = float(dropout_p)
+        seed_t = None
+        if dropout_p != 0.0 and dropout_threshold(dropout_p):
+            seed_t = (torch.empty(1, dtype=torch.int64, device=q.device).random_() if seed is None
+                      else _seed_tensor(seed, q.device))
+            rc = _hip.load().smt_attn_fwd_dropout(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
+                                                  ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
+                                                  lse.data_ptr(), km, km_ld, dropout_p, seed_t.data_ptr(),
+                                                  ctypes.byref(shape), _stream(q))
+            _hip._check(rc, "smt_attn_fwd_dropout")
+        else:
+            rc = _hip.load().smt_attn_fwd_kmask(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
+                                                ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
+                                                lse.data_ptr(), km, km_ld, ctypes.byref(shape), _stream(q))
+            _hip._check(rc, "smt_attn_fwd")
+        ctx.save_for_backward(q, k, v, o, lse, key_mask.bits if key_mask is not None else None, seed_t)
+        ctx.dropout_p = dropout_p
         ctx.scale = float(scale)
         ctx.joint = bool(joint)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, km = ctx.saved_tensors
+        q, k, v, o, lse, km, seed_t = ctx.saved_tensors
         B, Hq, S, D = q.shape
         Hkv = k.shape[1]
         do = do if (do.stride(-1) == 1 and not any(s % 8 for s in do.stride()[:3]) and do.data_ptr() % 16 == 0) \
@@ -836,6 +898,16 @@ class FlashAttnFn(torch.autograd.Function):
             do = do.to(q.dtype)
         shape = _hip.AttnShape(B, Hq, Hkv, S, ctx.scale, _dt(q))
         T = _attn_tensor
+        if seed_t is not None:
+            rc = _hip.load().smt_attn_bwd_dropout(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
+                                                  ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
+                                                  lse.data_ptr(), delta.data_ptr(), ctypes.byref(T(dq)),
+                                                  ctypes.byref(T(dk)), ctypes.byref(T(dv)),
+                                                  km.data_ptr() if km is not None else None,
+                                                  km.shape[1] if km is not None else 0, ctx.dropout_p,
+                                                  seed_t.data_ptr(), ctypes.byref(shape), _stream(q))
+            _hip._check(rc, "smt_attn_bwd_dropout")
+            return dq, dk, dv, None, None, None, None, None
         rc = _hip.load().smt_attn_bwd_kmask(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
                                             ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
                                             lse.data_ptr(), delta.data_ptr(), ctypes.byref(T(dq)),
@@ -843,31 +915,35 @@ class FlashAttnFn(torch.autograd.Function):
                                             km.data_ptr() if km is not None else None,
                                             km.shape[1] if km is not None else 0, ctypes.byref(shape), _stream(q))
         _hip._check(rc, "smt_attn_bwd")
-        return dq, dk, dv, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
-def flash_attention(q, k, v, scale=None, key_mask: "KeyMask" = None, joint: bool = False):
+def flash_attention(q, k, v, scale=None, key_mask: "KeyMask" = None, joint: bool = False, dropout_p: float = 0.0,
+                    seed=None):
     """Causal attention ``[B, Hq, S, 128]`` x ``[B, Hkv, S, 128]`` -> ``[B, S, Hq, 128]``; with
     ``key_mask`` the keys it clears take no part (padded batches). ``joint``: the gradients of q, k
-    and v go out as slices of one ``[B, S, (Hq + 2 Hkv) * 128]`` buffer (same values)."""
-    return FlashAttnFn.apply(q, k, v, scale if scale is not None else q.shape[-1] ** -0.5, key_mask, joint)
+    and v go out as slices of one ``[B, S, (Hq + 2 Hkv) * 128]`` buffer (same values). ``dropout_p``:
+    attention dropout applied inside the kernels, forward and backward (effective rate
+    :func:`dropout_effective_p`, mask :func:`flash_dropout_mask`); ``seed``: an int or a 1-element
+    int64 device tensor, drawn from the device generator when None."""
+    return FlashAttnFn.apply(q, k, v, scale if scale is not None else q.shape[-1] ** -0.5, key_mask, joint,
+                             dropout_p, seed)
 
 
 def smt_flash_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None,
                                 is_causal=None, **kwargs):
     """transformers attention-function signature (``AttentionInterface``). Causal self-attention,
     unpadded (``attention_mask`` None) or padded (a :class:`KeyMask` from :func:`smt_flash_mask`);
-    anything else raises rather than silently changing semantics."""
+    ``dropout`` (transformers passes the config's ``attention_dropout`` in training mode, 0.0 in eval)
+    runs inside the kernels; anything else raises rather than silently changing semantics."""
     if attention_mask is not None and not isinstance(attention_mask, KeyMask):
         raise NotImplementedError("smt_flash attention: only key-padding masks built by smt_flash_mask are "
                                   f"supported (got {type(attention_mask).__name__})")
-    if dropout:
-        raise NotImplementedError("smt_flash attention: dropout is not supported")
     if is_causal is False or not getattr(module, "is_causal", True):
         raise NotImplementedError("smt_flash attention: causal attention only")
     # the engine marks attention modules whose q/k/v_proj share a joint transposed copy
     return flash_attention(query, key, value, scaling, attention_mask,
-                           joint=getattr(module, "_smt_joint_qkv_grad", False)), None
+                           joint=getattr(module, "_smt_joint_qkv_grad", False), dropout_p=float(dropout or 0.0)), None
 
 
 def smt_flash_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_function=None,
