@@ -118,6 +118,34 @@ int smt_attn_bwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, con
 int smt_attn_dropout_mask(uint8_t* keep, float p, const uint64_t* seed, const smt_attn_shape* shape,
                           hipStream_t stream);
 
+/*
+ * Packed sequences (additive entry points; the ABI version is unchanged): several samples concatenated
+ * into one row, block-diagonal causal attention. doc_start, doc_end: device int32 [B][S];
+ * doc_start[b][i] is the index of the first token of token i's document, doc_end[b][i] one past its
+ * last token. Query q sees key j iff doc_start[q] <= j <= q. The forward and the dQ kernel test that
+ * rule; the dK / dV kernel, which owns keys, tests q < doc_end[j], the same set when the two arrays
+ * describe one partition of the row into documents.
+ *
+ * The kernels are memory-safe for any array contents: doc_start[i] is read clamped to [0, i] and
+ * doc_end[i] clamped to [i + 1, S], and the values only skip K/V tiles or query slices of the plain
+ * causal sweep and mask scores inside it. Inconsistent arrays give an unspecified result, never an
+ * access outside the tensors. Every row sees at least itself, so this path has no lse = +inf case.
+ *
+ * There is no key mask here: padding in a packed row is a trailing document of its own (whose labels
+ * the loss ignores). p, seed: as in smt_attn_*_dropout (the keep function does not depend on the
+ * documents; t == 0 is no dropout and seed may then be NULL). Both arrays NULL: the calls forward to
+ * smt_attn_fwd_dropout / smt_attn_bwd_dropout without a key mask. Exactly one array NULL returns -1
+ * before any HIP call.
+ */
+int smt_attn_fwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                      const smt_attn_tensor* o, float* lse, const int32_t* doc_start, const int32_t* doc_end,
+                      float p, const uint64_t* seed, const smt_attn_shape* shape, hipStream_t stream);
+int smt_attn_bwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                      const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
+                      const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
+                      const int32_t* doc_start, const int32_t* doc_end, float p, const uint64_t* seed,
+                      const smt_attn_shape* shape, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

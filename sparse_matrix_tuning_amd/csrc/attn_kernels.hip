@@ -1,6 +1,7 @@
 // Causal grouped-query flash attention for gfx950 (CDNA4), head_dim 128, bf16 or fp16 I/O (the model's
 // dtype, smt_attn_shape.dtype; ABI v13), fp32 softmax, optional attention dropout inside the three
-// kernels (DROP instances, smt_attn_*_dropout).
+// kernels (DROP instances, smt_attn_*_dropout), optional document mask of packed rows (DOC instances,
+// smt_attn_*_docs).
 // C ABI: include/smt_attention.h. Replaces transformers' sdpa attention (aotriton on this torch
 // build) in the LLaMA decoder that carries the SMT modules.
 //
@@ -269,6 +270,32 @@ constexpr int kTileB = kKV * kRowB;        // 16 KiB per operand tile
 // visible key is masked gets a zero output, lse = +inf and zero gradients (torch's safe softmax).
 __device__ __forceinline__ bool key_bit(uint64_t w, int key) { return (w >> (key & 63)) & 1ull; }
 
+// Document mask (optional, DOC instances, smt_attn_*_docs): several samples packed into one row, query
+// q sees key j iff doc_start[q] <= j <= q. The forward and dQ lanes hold one q, so they test
+// key < doc_start[q]; a dK/dV lane holds one key and tests q >= doc_end[key], the same set for
+// consistent arrays. Every value is clamped where it is read (doc_start[i] to [0, i], doc_end[i] to
+// [i + 1, S]) and only ever gates compute or selects a tile inside the sweep of the plain kernels, so no
+// array content can move an access outside the tensors.
+constexpr int kIntMax = 0x7fffffff;
+__device__ __forceinline__ int doc_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
+__device__ __forceinline__ int wave_min(int v) {           // wave-uniform (an SGPR)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+// The smallest clamped doc_start of rows [q0, q0 + rows) of one batch row, from every wave alike
+// (workgroup-uniform without a barrier): the K/V sweep of a forward / dQ workgroup starts at its tile.
+__device__ __forceinline__ int doc_block_min(const int32_t* ds, int q0, int rows, int S, int lane) {
+    int g = kIntMax;
+    for (int r = q0 + lane; r < min(q0 + rows, S); r += 64) g = min(g, doc_clamp(ds[r], 0, r));
+    return wave_min(g);
+}
+
 // Attention dropout (DROP instances, smt_attn_*_dropout; the keep function is documented in
 // include/smt_attention.h and is part of the contract). One 32-bit word decides 4 consecutive keys of
 // one query row, one byte each: keep = byte >= t. The forward and dQ lanes hold one q and runs of 4
@@ -307,6 +334,7 @@ struct FwdArgs {
     int B, Hq, Hkv, S;
     float sl2;                             // scale * log2(e)
     DropArgs drop;                         // read by the DROP instances only
+    const int32_t* doc_start;              // [B][S], read by the DOC instances only
 };
 
 // Causal balance: a workgroup takes the query blocks qb and nqb-1-qb (equal total work per workgroup).
@@ -351,7 +379,11 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
 // one wave per SIMD over 64 rows (two builds), all slower.
 // ------------------------------------------------------------------------------------------------
 
-template <bool KMASK, int F, bool DROP>
+// DOC: the sweep starts at the tile of the workgroup's smallest doc_start (an odd first tile runs once
+// through tile<1>, so the ring slot stays a compile-time parity); a wave skips the compute, never the
+// DMA, wait or barrier, of tiles wholly before its own rows' smallest doc_start, tests key <
+// doc_start[q] on the tiles below its rows' largest doc_start, and runs the plain body on the rest.
+template <bool KMASK, int F, bool DROP, bool DOC = false>
 struct FwdLean {
     const FwdArgs& a;
     uint8_t* lds;
@@ -363,6 +395,7 @@ struct FwdLean {
     float m_run, l_run;
     int qw, qrow, hi, l32, wave, lane, nt, last;
     uint32_t drop_rk;                      // DROP: the lane's row key
+    int doc_ds, doc_wmax, doc_t0;          // DOC: the lane's doc_start, the wave's largest, the wave's first tile
     TrLane tl;
 
     __device__ __forceinline__ FwdLean(const FwdArgs& a_, uint8_t* lds_) : a(a_), lds(lds_) {}
@@ -423,6 +456,15 @@ struct FwdLean {
                 }
             }
         }
+        if constexpr (DOC) {
+            if (k0 < doc_wmax) {                               // a document of this wave starts past k0
+#pragma unroll
+                for (int i = 0; i < 32; ++i) {
+                    const int key = k0 + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * hi;
+                    if (key < doc_ds) x[i] = kNegInf;
+                }
+            }
+        }
         float mx[11];
 #pragma unroll
         for (int i = 0; i < 10; ++i) mx[i] = max3f(x[3 * i], x[3 * i + 1], x[3 * i + 2]);
@@ -435,7 +477,7 @@ struct FwdLean {
         const bool move = m_tile > m_run + kFwdThr;
         const float m_new = move ? m_tile : m_run;
         const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.f;
-        const float m_use = (KMASK && m_new == kNegInf) ? 0.f : m_new;
+        const float m_use = ((KMASK || DOC) && m_new == kNegInf) ? 0.f : m_new;
         // packed fp32 (v_pk_fma_f32 / v_pk_add_f32: two lanes' worth per VALU issue)
         const f32x2_t sl2v = {a.sl2, a.sl2}, mv = {-m_use, -m_use};
         f32x2_t sm[16];
@@ -487,7 +529,7 @@ struct FwdLean {
     template <int SLOT>
     __device__ __forceinline__ void tile(int t) {
         if (t + 1 < nt) issue(t + 1);
-        if (t <= last) compute<SLOT, true>(t, t == last);
+        if (t <= last && (!DOC || t >= doc_t0)) compute<SLOT, true>(t, t == last);
         vm_wait_all();
         __syncthreads();
     }
@@ -524,13 +566,35 @@ struct FwdLean {
             for (int i = 0; i < 16; ++i) o[dt][i] = 0.f;
         m_run = kNegInf;
         l_run = 0.f;
-        issue(0);
+        int t0 = 0;                                            // the first tile of the sweep
+        if constexpr (DOC) {
+            const int32_t* ds = a.doc_start + (int64_t)b * a.S;
+            const bool qvalid = qrow < a.S;
+            doc_ds = qvalid ? doc_clamp(ds[qrow], 0, qrow) : 0;
+            doc_wmax = wave_max(doc_ds);
+            doc_t0 = wave_min(qvalid ? doc_ds : kIntMax) / kKV;        // a wave without a valid row: no tile
+            t0 = doc_block_min(ds, q0, kFwdQB, a.S, lane) / kKV;       // <= q0 / kKV < nt (row q0 is valid)
+            issue(t0);
+        } else {
+            issue(0);
+        }
         vm_wait_all();
         vm_wait_all_known();                                   // the Q fragments too (compiler-visible)
         __syncthreads();
-        for (int t = 0; t < nt; t += 2) {
-            tile<0>(t);
-            if (t + 1 < nt) tile<1>(t + 1);
+        if constexpr (DOC) {
+            if (t0 & 1) {                                      // an odd first tile: once through slot 1
+                tile<1>(t0);
+                ++t0;
+            }
+            for (int t = t0; t < nt; t += 2) {
+                tile<0>(t);
+                if (t + 1 < nt) tile<1>(t + 1);
+            }
+        } else {
+            for (int t = 0; t < nt; t += 2) {
+                tile<0>(t);
+                if (t + 1 < nt) tile<1>(t + 1);
+            }
         }
         const float l_tot = halves_sum(l_run);
         if (qrow < a.S) {
@@ -572,6 +636,24 @@ void attn_fwd_kernel(FwdArgs a) {
     fl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
 }
 
+// The DOC instances are kernels of their own with attn_fwd_kernel's body, so the plain ones keep their
+// names and their code.
+template <int F, bool DROP>
+__global__ __launch_bounds__(64 * kFwdWaves, 2)
+void attn_fwd_docs_kernel(FwdArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // K/V ring: 2 x 32 KiB
+    const int nqb = (a.S + kFwdQB - 1) / kFwdQB;
+    const int G = a.Hq / a.Hkv;
+    const int total = nqb * a.Hq * a.B;
+    const int L = xcd_logical(blockIdx.x, total);              // the order of attn_fwd_kernel
+    const int per_group = G * nqb;
+    const int grp = L / per_group;
+    const int rem = L - grp * per_group;
+    const int hk = grp % a.Hkv;
+    FwdLean<false, F, DROP, true> fl(a, lds);
+    fl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
+}
+
 // ------------------------------------------------------------------------------------------------
 // dQ: a workgroup = 4 waves x 32 query rows of one (b, q head), sweeping the K/V tiles up to the
 // diagonal (staged as in the forward). Per tile: S^T = K Q^T, dP^T = V dO^T, P = exp2(S*c - lse),
@@ -591,6 +673,7 @@ struct DqArgs {
     int B, Hq, Hkv, S;
     float sl2, scale;
     DropArgs drop;                         // read by the DROP instances only
+    const int32_t* doc_start;              // [B][S], read by the DOC instances only
 };
 
 // dQ (DqLean): a workgroup = 4 waves x 32 query rows of one (b, q head) sweeping the K/V tiles up to
@@ -599,7 +682,8 @@ struct DqArgs {
 // fp32, the causal test only on the wave's diagonal tile, scheduling fences that bound the fragment
 // reads hoisted ahead. Measured and removed (git history): one wave per SIMD with AGPR
 // accumulators, and dQ as a GEMM over a materialised dS, both slower.
-template <bool KMASK, int F, bool DROP>
+// DOC: as in the forward (FwdLean).
+template <bool KMASK, int F, bool DROP, bool DOC = false>
 struct DqLean {
     const DqArgs& a;
     uint8_t* lds;
@@ -610,6 +694,7 @@ struct DqLean {
     __amdgpu_buffer_rsrc_t rk, rv;
     uint32_t lds0, lo_row, lo_t0, lo_t4;
     uint32_t drop_rk;                      // DROP: the lane's row key
+    int doc_ds, doc_wmax, doc_t0;          // DOC: the lane's doc_start, the wave's largest, the wave's first tile
     int lane, wave, hi, l32, qw, qrow, nt, last;
 
     __device__ __forceinline__ DqLean(const DqArgs& a_, uint8_t* lds_) : a(a_), lds(lds_) {}
@@ -666,6 +751,15 @@ struct DqLean {
                 }
             }
         }
+        if constexpr (DOC) {
+            if (k0 < doc_wmax) {                               // a document of this wave starts past k0
+#pragma unroll
+                for (int i = 0; i < 32; ++i) {
+                    const int key = k0 + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * hi;
+                    if (key < doc_ds) pr[i] = 0.f;
+                }
+            }
+        }
         if constexpr (DROP) {                                  // dS = P (M dP r - delta)
             const uint32_t kt0 = ((uint32_t)(k0 >> 2) + (uint32_t)hi) * kDropKeyMul;
 #pragma unroll
@@ -698,7 +792,7 @@ struct DqLean {
     template <int SLOT>
     __device__ __forceinline__ void tile(int t) {
         if (t + 1 < nt) issue(t + 1);
-        if (t <= last) compute<SLOT>(t, t == last);
+        if (t <= last && (!DOC || t >= doc_t0)) compute<SLOT>(t, t == last);
         vm_wait_all();
         __syncthreads();
     }
@@ -765,13 +859,34 @@ struct DqLean {
         for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
             for (int i = 0; i < 16; ++i) dq[dt][i] = 0.f;
-        if (nt > 0) issue(0);
+        int t0 = 0;                                            // the first tile of the sweep
+        if constexpr (DOC) {
+            const int32_t* ds = a.doc_start + (int64_t)b * a.S;
+            doc_ds = qvalid ? doc_clamp(ds[qrow], 0, qrow) : 0;
+            doc_wmax = wave_max(doc_ds);
+            doc_t0 = wave_min(qvalid ? doc_ds : kIntMax) / kKV;        // a wave without a valid row: no tile
+            t0 = doc_block_min(ds, q0, kDqQB, a.S, lane) / kKV;        // <= q0 / kKV < nt (row q0 is valid)
+            issue(t0);
+        } else {
+            if (nt > 0) issue(0);
+        }
         vm_wait_all();
         vm_wait_all_known();
         __syncthreads();
-        for (int t = 0; t < nt; t += 2) {
-            tile<0>(t);
-            if (t + 1 < nt) tile<1>(t + 1);
+        if constexpr (DOC) {
+            if (t0 & 1) {                                      // an odd first tile: once through slot 1
+                tile<1>(t0);
+                ++t0;
+            }
+            for (int t = t0; t < nt; t += 2) {
+                tile<0>(t);
+                if (t + 1 < nt) tile<1>(t + 1);
+            }
+        } else {
+            for (int t = 0; t < nt; t += 2) {
+                tile<0>(t);
+                if (t + 1 < nt) tile<1>(t + 1);
+            }
         }
         if (qvalid) {
             uint16_t* out = a.dq + b * a.dq_sb + h * a.dq_sh + (int64_t)qrow * a.dq_ss;
@@ -804,6 +919,22 @@ void attn_dq_kernel(DqArgs a) {
     const int rem = L - grp * per_group;
     const int hk = grp % a.Hkv;
     DqLean<KMASK, F, DROP> dl(a, lds);
+    dl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
+}
+
+template <int F, bool DROP>
+__global__ __launch_bounds__(64 * kDqWaves, 8 / kDqWaves)
+void attn_dq_docs_kernel(DqArgs a) {                           // attn_dq_kernel's body with DOC
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // 64 KiB
+    const int nqb = (a.S + kDqQB - 1) / kDqQB;
+    const int G = a.Hq / a.Hkv;
+    const int total = nqb * a.Hq * a.B;
+    const int L = xcd_logical(blockIdx.x, total);
+    const int per_group = G * nqb;
+    const int grp = L / per_group;
+    const int rem = L - grp * per_group;
+    const int hk = grp % a.Hkv;
+    DqLean<false, F, DROP, true> dl(a, lds);
     dl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
 }
 
@@ -840,6 +971,7 @@ struct DkvArgs {
     int B, Hq, Hkv, S;
     float sl2, scale;
     DropArgs drop;                         // read by the DROP instances only
+    const int32_t* doc_end;                // [B][S], read by the DOC instances only
 };
 
 // dK / dV (DkvLean): the slice loop unrolled by two so that the ring slot is a compile-time LDS offset (the ring now sits in front of the V
@@ -863,7 +995,11 @@ template <int C>
 __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, C * 0x55, 0xf, 0xf, true);
 }
-template <bool KMASK, int F, bool DROP>
+// DOC: key on the lane, so the test is q >= doc_end[key] with the lane's own clamped doc_end (no
+// per-slice data to stage). The sweep ends at doc_end of the block's last valid key instead of S
+// (workgroup-uniform: it sizes n_sl, hence every issue, wait and barrier); a wave skips the compute
+// of slices at or past its keys' largest doc_end and tests only slices that reach past their smallest.
+template <bool KMASK, int F, bool DROP, bool DOC = false>
 struct DkvLean {
     const DkvArgs& a;
     uint8_t* lds;
@@ -875,6 +1011,7 @@ struct DkvLean {
     uint32_t lo_row, lo_v, lo_t0, lo_t4;      // lane constants of the row / V-row / transposed reads
     uint64_t drop_seed;                       // DROP: the seed, the lane's (key >> 2) term and key & 3
     uint32_t drop_kt, drop_klo;
+    int doc_de, doc_wmin, doc_wmax;           // DOC: the lane's doc_end, the wave's smallest and largest
 
     __device__ __forceinline__ DkvLean(const DkvArgs& a_, uint8_t* lds_) : a(a_), lds(lds_) {}
 
@@ -913,6 +1050,7 @@ struct DkvLean {
     __device__ __forceinline__ int slice_s0(int it) const {
         const int sl = n_sl - 1 - it % n_sl;               // descending q: the longest causal rows first
         const int s0 = k0 + sl * kSlice;
+        if (DOC && s0 >= doc_wmax) return -1;
         return (s0 + kSlice - 1 < kw) ? -1 : s0;
     }
 
@@ -962,6 +1100,15 @@ struct DkvLean {
         if (KMASK && !kvalid) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) pr[i] = 0.f;
+        }
+        if constexpr (DOC) {
+            if (s0 + kSlice > doc_wmin) {                  // a document of this wave ends inside or before the slice
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int q = s0 + (i & 3) + 8 * (i >> 2) + 4 * hi;
+                    if (q >= doc_de) pr[i] = 0.f;
+                }
+            }
         }
         bool kp[16];                                       // DROP: element i is kept
         if constexpr (DROP) {
@@ -1073,7 +1220,17 @@ struct DkvLean {
             if (key < a.S) kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + (int64_t)key * a.k.ss + 16 * ks + 8 * hi);
             else kf[ks] = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
         }
-        n_sl = (a.S - k0 + kSlice - 1) / kSlice;
+        int s_end = a.S;
+        if constexpr (DOC) {
+            const int32_t* de = a.doc_end + (int64_t)b * a.S;
+            const bool valid = key < a.S;
+            doc_de = valid ? doc_clamp(de[key], key + 1, a.S) : kIntMax;
+            doc_wmin = wave_min(doc_de);
+            doc_wmax = wave_max(valid ? doc_de : 0);       // a wave without a valid key: no slice
+            const int lk = min(k0 + kKB, a.S) - 1;         // the block's last valid key (k0 < S)
+            s_end = doc_clamp(__builtin_amdgcn_readfirstlane(de[lk]), lk + 1, a.S);
+        }
+        n_sl = (s_end - k0 + kSlice - 1) / kSlice;
         n_it = G * n_sl;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
@@ -1130,6 +1287,21 @@ void attn_dkdv_kernel(DkvArgs a) {
     }
 }
 
+template <int F, bool DROP>
+__global__ __launch_bounds__(kDkvWaves * 64, 2)
+void attn_dkdv_docs_kernel(DkvArgs a) {                        // attn_dkdv_kernel's body with DOC
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kVImg + kDkvLeanRing * (kSliceBuf + (DROP ? kDropRkB : 0))];
+    const int nkb = (a.S + kKB - 1) / kKB;
+    const int total = ((nkb + 1) / 2) * a.Hkv * a.B;
+    const PairTask t = pair_task(xcd_logical(blockIdx.x, total), nkb, 1, a.Hkv);
+#pragma nounroll
+    for (int i = 0; i < t.n; ++i) {
+        if (i) __syncthreads();
+        DkvLean<false, F, DROP, true> dl(a, lds);
+        dl.run(t.b, t.hk, t.blk[1 - i]);
+    }
+}
+
 // The keep mask of every (b, h, q, key) as bytes (smt_attn_dropout_mask): one thread per 4-key word.
 __global__ __launch_bounds__(256)
 void attn_dropout_mask_kernel(uint8_t* keep, DropArgs drop, int S, int64_t n_words) {
@@ -1182,6 +1354,18 @@ int check_shape(const smt_attn_shape* s, const char* fn) {
         else SMT_ATTN_LAUNCH_KD(kernel, SMT_DTYPE_BF16, kmask, drop, grid, block, stream, args);             \
     } while (0)
 
+// the (format, dropout) instance of a document-mask kernel
+#define SMT_ATTN_LAUNCH_DOCS(kernel, dtype, drop, grid, block, stream, args)                                     \
+    do {                                                                                                      \
+        if ((dtype) == SMT_DTYPE_FP16) {                                                                      \
+            if (drop) hipLaunchKernelGGL((kernel<SMT_DTYPE_FP16, true>), grid, block, 0, stream, args);      \
+            else hipLaunchKernelGGL((kernel<SMT_DTYPE_FP16, false>), grid, block, 0, stream, args);          \
+        } else {                                                                                              \
+            if (drop) hipLaunchKernelGGL((kernel<SMT_DTYPE_BF16, true>), grid, block, 0, stream, args);      \
+            else hipLaunchKernelGGL((kernel<SMT_DTYPE_BF16, false>), grid, block, 0, stream, args);          \
+        }                                                                                                     \
+    } while (0)
+
 Tns tns(const smt_attn_tensor* t) { return Tns{static_cast<const uint16_t*>(t->ptr), t->sb, t->sh, t->ss}; }
 
 // t of the keep function, or -1 for p outside [0, 1) or NaN
@@ -1202,10 +1386,17 @@ int check_drop(float p, const uint64_t* seed, const char* fn, DropArgs* d) {
     return 0;
 }
 
-// fn: the entry point's name for messages; drop.t == 0: the plain kernels
+// doc_start / doc_end of a *_docs call (both set, never with a key mask)
+struct DocArgs {
+    const int32_t* start;
+    const int32_t* end;
+};
+constexpr DocArgs kNoDocs = {nullptr, nullptr};
+
+// fn: the entry point's name for messages; drop.t == 0: the plain kernels; docs.start: the DOC kernels
 int attn_fwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
              const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld, DropArgs drop,
-             const smt_attn_shape* shape, hipStream_t stream) {
+             DocArgs docs, const smt_attn_shape* shape, hipStream_t stream) {
     int rc;
     if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
         (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)))
@@ -1221,18 +1412,23 @@ int attn_fwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
     a.B = shape->B; a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.S = shape->S;
     a.sl2 = shape->scale * 1.4426950408889634f;
     a.drop = drop;
+    a.doc_start = docs.start;
     const int64_t nqb = (shape->S + kFwdQB - 1) / kFwdQB;
     const int64_t blocks = nqb * shape->Hq * shape->B;
     if (blocks > 0x7fffffffLL) return fail(-1, "%s: too many blocks", fn);
-    SMT_ATTN_LAUNCH(attn_fwd_kernel, key_mask, shape->dtype, drop.t != 0, dim3((unsigned)blocks), dim3(64 * kFwdWaves),
-                    stream, a);
+    if (docs.start)
+        SMT_ATTN_LAUNCH_DOCS(attn_fwd_docs_kernel, shape->dtype, drop.t != 0, dim3((unsigned)blocks),
+                             dim3(64 * kFwdWaves), stream, a);
+    else
+        SMT_ATTN_LAUNCH(attn_fwd_kernel, key_mask, shape->dtype, drop.t != 0, dim3((unsigned)blocks),
+                        dim3(64 * kFwdWaves), stream, a);
     return check_launch("attn_fwd_kernel");
 }
 
 int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
              const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
              const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
-             const uint64_t* key_mask, int64_t key_mask_ld, DropArgs drop, const smt_attn_shape* shape,
+             const uint64_t* key_mask, int64_t key_mask_ld, DropArgs drop, DocArgs docs, const smt_attn_shape* shape,
              hipStream_t stream) {
     int rc;
     if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
@@ -1254,9 +1450,11 @@ int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
     qa.kmask = key_mask; qa.kmask_ld = key_mask_ld;
     qa.B = B; qa.Hq = Hq; qa.Hkv = Hkv; qa.S = S; qa.sl2 = sl2; qa.scale = shape->scale;
     qa.drop = drop;
+    qa.doc_start = docs.start;
     const int64_t nqb = (S + kDqQB - 1) / kDqQB;
     const dim3 qgrid((unsigned)(nqb * Hq * B)), qblock(64 * kDqWaves);
-    SMT_ATTN_LAUNCH(attn_dq_kernel, key_mask, shape->dtype, dropping, qgrid, qblock, stream, qa);
+    if (docs.start) SMT_ATTN_LAUNCH_DOCS(attn_dq_docs_kernel, shape->dtype, dropping, qgrid, qblock, stream, qa);
+    else SMT_ATTN_LAUNCH(attn_dq_kernel, key_mask, shape->dtype, dropping, qgrid, qblock, stream, qa);
     if ((rc = check_launch("attn_dq_kernel"))) return rc;
 
     DkvArgs ka;
@@ -1267,9 +1465,11 @@ int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
     ka.kmask = key_mask; ka.kmask_ld = key_mask_ld;
     ka.B = B; ka.Hq = Hq; ka.Hkv = Hkv; ka.S = S; ka.sl2 = sl2; ka.scale = shape->scale;
     ka.drop = drop;
+    ka.doc_end = docs.end;
     const int64_t nkb = (S + kKB - 1) / kKB;
     const dim3 grid((unsigned)(((nkb + 1) / 2) * Hkv * B));
-    SMT_ATTN_LAUNCH(attn_dkdv_kernel, key_mask, shape->dtype, dropping, grid, dim3(kDkvWaves * 64), stream, ka);
+    if (docs.start) SMT_ATTN_LAUNCH_DOCS(attn_dkdv_docs_kernel, shape->dtype, dropping, grid, dim3(kDkvWaves * 64), stream, ka);
+    else SMT_ATTN_LAUNCH(attn_dkdv_kernel, key_mask, shape->dtype, dropping, grid, dim3(kDkvWaves * 64), stream, ka);
     return check_launch("attn_dkdv_kernel");
 }
 
@@ -1286,7 +1486,7 @@ int smt_attn_fwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const
                        const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
                        const smt_attn_shape* shape, hipStream_t stream) {
     return attn_fwd(key_mask ? "smt_attn_fwd_kmask" : "smt_attn_fwd", q, k, v, o, lse, key_mask, key_mask_ld, kNoDrop,
-                    shape, stream);
+                    kNoDocs, shape, stream);
 }
 
 int smt_attn_fwd(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1300,7 +1500,7 @@ int smt_attn_bwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const
                        const uint64_t* key_mask, int64_t key_mask_ld, const smt_attn_shape* shape,
                        hipStream_t stream) {
     return attn_bwd(key_mask ? "smt_attn_bwd_kmask" : "smt_attn_bwd", q, k, v, o, d_o, lse, delta_ws, dq, dk, dv,
-                    key_mask, key_mask_ld, kNoDrop, shape, stream);
+                    key_mask, key_mask_ld, kNoDrop, kNoDocs, shape, stream);
 }
 
 int smt_attn_bwd(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1319,7 +1519,7 @@ int smt_attn_fwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, con
     int rc;
     if ((rc = check_drop(p, seed, "smt_attn_fwd_dropout", &drop))) return rc;
     if (drop.t == 0) return smt_attn_fwd_kmask(q, k, v, o, lse, key_mask, key_mask_ld, shape, stream);
-    return attn_fwd("smt_attn_fwd_dropout", q, k, v, o, lse, key_mask, key_mask_ld, drop, shape, stream);
+    return attn_fwd("smt_attn_fwd_dropout", q, k, v, o, lse, key_mask, key_mask_ld, drop, kNoDocs, shape, stream);
 }
 
 int smt_attn_bwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1332,7 +1532,35 @@ int smt_attn_bwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, con
     if ((rc = check_drop(p, seed, "smt_attn_bwd_dropout", &drop))) return rc;
     if (drop.t == 0)
         return smt_attn_bwd_kmask(q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, key_mask, key_mask_ld, shape, stream);
-    return attn_bwd("smt_attn_bwd_dropout", q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, key_mask, key_mask_ld, drop, shape,
+    return attn_bwd("smt_attn_bwd_dropout", q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, key_mask, key_mask_ld, drop, kNoDocs,
+                    shape, stream);
+}
+
+int smt_attn_fwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                      const smt_attn_tensor* o, float* lse, const int32_t* doc_start, const int32_t* doc_end, float p,
+                      const uint64_t* seed, const smt_attn_shape* shape, hipStream_t stream) {
+    const char* fn = "smt_attn_fwd_docs";
+    if (!doc_start != !doc_end) return fail(-1, "%s: doc_start and doc_end come together (one is null)", fn);
+    if (!doc_start) return smt_attn_fwd_dropout(q, k, v, o, lse, nullptr, 0, p, seed, shape, stream);
+    DropArgs drop;
+    int rc;
+    if ((rc = check_drop(p, seed, fn, &drop))) return rc;
+    return attn_fwd(fn, q, k, v, o, lse, nullptr, 0, drop, DocArgs{doc_start, doc_end}, shape, stream);
+}
+
+int smt_attn_bwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                      const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
+                      const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
+                      const int32_t* doc_start, const int32_t* doc_end, float p, const uint64_t* seed,
+                      const smt_attn_shape* shape, hipStream_t stream) {
+    const char* fn = "smt_attn_bwd_docs";
+    if (!doc_start != !doc_end) return fail(-1, "%s: doc_start and doc_end come together (one is null)", fn);
+    if (!doc_start)
+        return smt_attn_bwd_dropout(q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, nullptr, 0, p, seed, shape, stream);
+    DropArgs drop;
+    int rc;
+    if ((rc = check_drop(p, seed, fn, &drop))) return rc;
+    return attn_bwd(fn, q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, nullptr, 0, drop, DocArgs{doc_start, doc_end}, shape,
                     stream);
 }
 

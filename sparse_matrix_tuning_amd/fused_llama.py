@@ -775,6 +775,74 @@ class KeyMask:
         return cls(bits.contiguous(), S)
 
 
+class DocMask:
+    """The document mask of packed rows as the smt_flash kernels take it (include/smt_attention.h,
+    ``smt_attn_*_docs``): several samples concatenated into one row, block-diagonal causal attention.
+    ``start`` / ``end``: int32 [B, S]; ``start[b, i]`` is the index of the first token of token i's
+    document, ``end[b, i]`` one past its last token; query q sees key j iff ``start[q] <= j <= q``.
+    The constructors use tensor ops only (no host synchronisation) and work on any device. Padding in
+    a packed row is a trailing document of its own, with labels of -100."""
+
+    __slots__ = ("start", "end", "S")
+
+    def __init__(self, start: torch.Tensor, end: torch.Tensor, S: int):
+        self.start, self.end, self.S = start, end, int(S)
+
+    @classmethod
+    def _from_first(cls, first: torch.Tensor) -> "DocMask":
+        """``first`` bool [B, S]: token i opens a document (column 0 always does)."""
+        B, S = first.shape
+        first = first.clone()
+        first[:, 0] = True
+        idx = torch.arange(S, dtype=torch.int32, device=first.device).expand(B, S)
+        start = torch.where(first, idx, torch.zeros_like(idx)).cummax(-1).values
+        last = torch.cat([first[:, 1:], first.new_ones(B, 1)], dim=1)            # token i closes a document
+        end = torch.where(last, idx + 1, torch.full_like(idx, S)).flip(-1).cummin(-1).values.flip(-1)
+        return cls(start.to(torch.int32).contiguous(), end.to(torch.int32).contiguous(), S)
+
+    @classmethod
+    def from_position_ids(cls, position_ids: torch.Tensor) -> "DocMask":
+        """A new document starts wherever the position does not follow the previous one by 1
+        (transformers' ``find_packed_sequence_indices``). ``position_ids``: [B, S]."""
+        pos = position_ids
+        if pos.dim() != 2:
+            raise ValueError(f"DocMask.from_position_ids: [B, S] position ids expected, got {tuple(pos.shape)}")
+        first = torch.cat([pos.new_ones(pos.shape[0], 1, dtype=torch.bool), pos[:, 1:] - pos[:, :-1] != 1], dim=1)
+        return cls._from_first(first)
+
+    @classmethod
+    def from_sequence_ids(cls, ids: torch.Tensor) -> "DocMask":
+        """A new document starts wherever the id differs from the previous token's. ``ids``: [B, S]."""
+        if ids.dim() != 2:
+            raise ValueError(f"DocMask.from_sequence_ids: [B, S] ids expected, got {tuple(ids.shape)}")
+        first = torch.cat([ids.new_ones(ids.shape[0], 1, dtype=torch.bool), ids[:, 1:] != ids[:, :-1]], dim=1)
+        return cls._from_first(first)
+
+    @classmethod
+    def from_cu_seqlens(cls, cu_seqlens, B: int, S: int, device=None) -> "DocMask":
+        """Cumulative document lengths ``[0, l0, l0 + l1, ..., S]`` (the flash-attention varlen
+        convention): one 1-D tensor or list for ``B == 1``, or a list of B of them. Tokens past the
+        last entry belong to the last document."""
+        rows = cu_seqlens
+        if isinstance(rows, torch.Tensor):
+            rows = [rows] if rows.dim() == 1 else list(rows)
+        elif len(rows) == 0 or not isinstance(rows[0], (list, tuple, torch.Tensor)):
+            rows = [rows]
+        if len(rows) != B:
+            raise ValueError(f"DocMask.from_cu_seqlens: {len(rows)} rows of cu_seqlens for a batch of {B}")
+        if device is None:
+            device = next((r.device for r in rows if isinstance(r, torch.Tensor)), torch.device("cpu"))
+        first = torch.zeros(B, S + 1, dtype=torch.bool, device=device)             # column S takes the closing S
+        for b, r in enumerate(rows):
+            r = torch.as_tensor(r, dtype=torch.int64, device=device).clamp(0, S)
+            first[b].index_fill_(0, r, True)
+        return cls._from_first(first[:, :S])
+
+
+_DOC_AND_KEY_MASK = ("flash attention: a document mask and a key mask together are not supported; padding in a "
+                     "packed row is expressed as a trailing document of its own, whose labels are -100")
+
+
 def dropout_threshold(p: float) -> int:
     """The 8-bit threshold ``t`` of the attention-dropout keep function (include/smt_attention.h):
     ``clamp(floor(p * 256 + 0.5), 0, 255)``; ``p`` outside [0, 1) raises."""
@@ -825,13 +893,16 @@ def flash_dropout_mask(B: int, Hq: int, S: int, p: float, seed, device) -> torch
 class FlashAttnFn(torch.autograd.Function):
     """Causal GQA attention: q [B, Hq, S, 128], k / v [B, Hkv, S, 128] (any strides with head_dim
     innermost) -> o [B, S, Hq, 128] (the layout transformers' attention functions return).
-    ``key_mask``: optional :class:`KeyMask` (padded batches). ``dropout_p``: attention dropout inside
+    ``key_mask``: optional :class:`KeyMask` (padded batches); ``doc_mask``: optional :class:`DocMask`
+    (packed rows; not together with a key mask). ``dropout_p``: attention dropout inside
     the kernels (the keep function of include/smt_attention.h; effective rate
     :func:`dropout_effective_p`); ``seed``: an int or a 1-element int64 device tensor, drawn from the
     device generator when None (no host sync; ``torch.utils.checkpoint`` replays it)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, key_mask=None, joint=False, dropout_p=0.0, seed=None):
+    def forward(ctx, q, k, v, scale, key_mask=None, joint=False, dropout_p=0.0, seed=None, doc_mask=None):
+        if doc_mask is not None and key_mask is not None:
+            raise NotImplementedError(_DOC_AND_KEY_MASK)
         for t, n in ((q, "q"), (k, "k"), (v, "v")):
             _need(t, "flash attention " + n, like=q)
         B, Hq, S, D = q.shape
@@ -853,11 +924,27 @@ class FlashAttnFn(torch.autograd.Function):
                 raise ValueError(f"flash attention: key mask for [{key_mask.bits.shape[0]}, {key_mask.S}] keys, "
                                  f"batch has [{B}, {S}]")
             km, km_ld = key_mask.bits.data_ptr(), key_mask.bits.shape[1]
+        ds = de = None
+        if doc_mask is not None:
+            ds, de = doc_mask.start, doc_mask.end
+            for t in (ds, de):
+                if t.shape != (B, S) or t.dtype != torch.int32 or t.device != q.device or not t.is_contiguous():
+                    raise ValueError(f"flash attention: document mask arrays must be contiguous int32 [{B}, {S}] on "
+                                     f"q's device (got {t.dtype} {tuple(t.shape)} on {t.device})")
         dropout_p = float(dropout_p)
         seed_t = None
         if dropout_p != 0.0 and dropout_threshold(dropout_p):
             seed_t = (torch.empty(1, dtype=torch.int64, device=q.device).random_() if seed is None
                       else _seed_tensor(seed, q.device))
+        if doc_mask is not None:
+            rc = _hip.load().smt_attn_fwd_docs(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
+                                               ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
+                                               lse.data_ptr(), ds.data_ptr(), de.data_ptr(),
+                                               dropout_p if seed_t is not None else 0.0,
+                                               seed_t.data_ptr() if seed_t is not None else None,
+                                               ctypes.byref(shape), _stream(q))
+            _hip._check(rc, "smt_attn_fwd_docs")
+        elif seed_t is not None:
             rc = _hip.load().smt_attn_fwd_dropout(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
                                                   ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
                                                   lse.data_ptr(), km, km_ld, dropout_p, seed_t.data_ptr(),
@@ -868,7 +955,7 @@ class FlashAttnFn(torch.autograd.Function):
                                                 ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
                                                 lse.data_ptr(), km, km_ld, ctypes.byref(shape), _stream(q))
             _hip._check(rc, "smt_attn_fwd")
-        ctx.save_for_backward(q, k, v, o, lse, key_mask.bits if key_mask is not None else None, seed_t)
+        ctx.save_for_backward(q, k, v, o, lse, key_mask.bits if key_mask is not None else None, seed_t, ds, de)
         ctx.dropout_p = dropout_p
         ctx.scale = float(scale)
         ctx.joint = bool(joint)
@@ -876,7 +963,7 @@ class FlashAttnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, km, seed_t = ctx.saved_tensors
+        q, k, v, o, lse, km, seed_t, ds, de = ctx.saved_tensors
         B, Hq, S, D = q.shape
         Hkv = k.shape[1]
         do = do if (do.stride(-1) == 1 and not any(s % 8 for s in do.stride()[:3]) and do.data_ptr() % 16 == 0) \
@@ -898,6 +985,16 @@ class FlashAttnFn(torch.autograd.Function):
             do = do.to(q.dtype)
         shape = _hip.AttnShape(B, Hq, Hkv, S, ctx.scale, _dt(q))
         T = _attn_tensor
+        if ds is not None:
+            rc = _hip.load().smt_attn_bwd_docs(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
+                                               ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
+                                               lse.data_ptr(), delta.data_ptr(), ctypes.byref(T(dq)),
+                                               ctypes.byref(T(dk)), ctypes.byref(T(dv)), ds.data_ptr(), de.data_ptr(),
+                                               ctx.dropout_p if seed_t is not None else 0.0,
+                                               seed_t.data_ptr() if seed_t is not None else None,
+                                               ctypes.byref(shape), _stream(q))
+            _hip._check(rc, "smt_attn_bwd_docs")
+            return dq, dk, dv, None, None, None, None, None, None
         if seed_t is not None:
             rc = _hip.load().smt_attn_bwd_dropout(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
                                                   ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
@@ -907,7 +1004,7 @@ class FlashAttnFn(torch.autograd.Function):
                                                   km.shape[1] if km is not None else 0, ctx.dropout_p,
                                                   seed_t.data_ptr(), ctypes.byref(shape), _stream(q))
             _hip._check(rc, "smt_attn_bwd_dropout")
-            return dq, dk, dv, None, None, None, None, None
+            return dq, dk, dv, None, None, None, None, None, None
         rc = _hip.load().smt_attn_bwd_kmask(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
                                             ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
                                             lse.data_ptr(), delta.data_ptr(), ctypes.byref(T(dq)),
@@ -915,35 +1012,70 @@ class FlashAttnFn(torch.autograd.Function):
                                             km.data_ptr() if km is not None else None,
                                             km.shape[1] if km is not None else 0, ctypes.byref(shape), _stream(q))
         _hip._check(rc, "smt_attn_bwd")
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def flash_attention(q, k, v, scale=None, key_mask: "KeyMask" = None, joint: bool = False, dropout_p: float = 0.0,
-                    seed=None):
+                    seed=None, doc_mask: "DocMask" = None):
     """Causal attention ``[B, Hq, S, 128]`` x ``[B, Hkv, S, 128]`` -> ``[B, S, Hq, 128]``; with
     ``key_mask`` the keys it clears take no part (padded batches). ``joint``: the gradients of q, k
     and v go out as slices of one ``[B, S, (Hq + 2 Hkv) * 128]`` buffer (same values). ``dropout_p``:
     attention dropout applied inside the kernels, forward and backward (effective rate
     :func:`dropout_effective_p`, mask :func:`flash_dropout_mask`); ``seed``: an int or a 1-element
-    int64 device tensor, drawn from the device generator when None."""
+    int64 device tensor, drawn from the device generator when None. ``doc_mask``: a :class:`DocMask`
+    for packed rows (block-diagonal causal attention; the kernels skip the K/V tiles no row of a
+    workgroup sees); not together with ``key_mask``."""
+    if doc_mask is not None and key_mask is not None:
+        raise NotImplementedError(_DOC_AND_KEY_MASK)
     return FlashAttnFn.apply(q, k, v, scale if scale is not None else q.shape[-1] ** -0.5, key_mask, joint,
-                             dropout_p, seed)
+                             dropout_p, seed, doc_mask)
 
 
 def smt_flash_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None,
                                 is_causal=None, **kwargs):
     """transformers attention-function signature (``AttentionInterface``). Causal self-attention,
-    unpadded (``attention_mask`` None) or padded (a :class:`KeyMask` from :func:`smt_flash_mask`);
+    unpadded (``attention_mask`` None), padded (a :class:`KeyMask` from :func:`smt_flash_mask`) or
+    packed (a :class:`DocMask` from :func:`smt_flash_mask` or built by the caller);
     ``dropout`` (transformers passes the config's ``attention_dropout`` in training mode, 0.0 in eval)
     runs inside the kernels; anything else raises rather than silently changing semantics."""
-    if attention_mask is not None and not isinstance(attention_mask, KeyMask):
-        raise NotImplementedError("smt_flash attention: only key-padding masks built by smt_flash_mask are "
-                                  f"supported (got {type(attention_mask).__name__})")
+    if attention_mask is not None and not isinstance(attention_mask, (KeyMask, DocMask)):
+        raise NotImplementedError("smt_flash attention: only key-padding and document masks built by smt_flash_mask "
+                                  f"are supported (got {type(attention_mask).__name__})")
     if is_causal is False or not getattr(module, "is_causal", True):
         raise NotImplementedError("smt_flash attention: causal attention only")
     # the engine marks attention modules whose q/k/v_proj share a joint transposed copy
-    return flash_attention(query, key, value, scaling, attention_mask,
-                           joint=getattr(module, "_smt_joint_qkv_grad", False), dropout_p=float(dropout or 0.0)), None
+    docs = attention_mask if isinstance(attention_mask, DocMask) else None
+    return flash_attention(query, key, value, scaling, None if docs is not None else attention_mask,
+                           joint=getattr(module, "_smt_joint_qkv_grad", False), dropout_p=float(dropout or 0.0),
+                           doc_mask=docs), None
+
+
+def _closure_vars(fn) -> dict:
+    cells = getattr(fn, "__closure__", None) or ()
+    names = getattr(getattr(fn, "__code__", None), "co_freevars", ())
+    return dict(zip(names, (c.cell_contents for c in cells)))
+
+
+def _packed_sequence_ids(mask_function):
+    """The [B, S] id tensor when ``mask_function`` is exactly what transformers' ``create_causal_mask``
+    builds for a packed batch, ``and_masks(causal_mask_function, packed_sequence_mask_function(ids))``,
+    else None. Recognised by structure (the closures), never by calling it: a sliding-window function
+    answers "token q sees q-1" as well, and a call could not tell a user's extra mask apart."""
+    from transformers import masking_utils as mu
+    if getattr(mask_function, "__code__", None) is not _inner_code(mu.and_masks, "and_mask"):
+        return None
+    parts = _closure_vars(mask_function).get("mask_functions")
+    if not isinstance(parts, tuple) or len(parts) != 2 or parts[0] is not mu.causal_mask_function:
+        return None
+    if getattr(parts[1], "__code__", None) is not _inner_code(mu.packed_sequence_mask_function, "inner_mask"):
+        return None
+    ids = _closure_vars(parts[1]).get("packed_sequence_mask")
+    return ids if isinstance(ids, torch.Tensor) and ids.dim() == 2 else None
+
+
+def _inner_code(factory, name: str):
+    """The code object of the function ``name`` that ``factory`` defines and returns."""
+    return next((c for c in factory.__code__.co_consts if getattr(c, "co_name", None) == name), None)
 
 
 def smt_flash_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_function=None,
@@ -951,13 +1083,26 @@ def smt_flash_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mas
     """transformers mask-interface builder for ``smt_flash`` (what ``create_causal_mask`` calls):
     ``None`` for a plain causal batch (no mask, or every key valid), a :class:`KeyMask` for a padded
     one: the causal mask AND the 2-D padding mask, exactly the mask ``sdpa_mask`` would materialise
-    as [B, 1, S, S]. Anything the kernels do not implement (a KV cache / offsets, packed sequences,
-    custom mask functions) raises."""
+    as [B, 1, S, S]; a :class:`DocMask` for a packed batch (restarting ``position_ids`` and no
+    ``attention_mask``: transformers hands over causal AND ``packed_sequence_mask_function(ids)``).
+    Anything the kernels do not implement (a KV cache / offsets, sliding windows, custom mask
+    functions) raises."""
     from transformers.masking_utils import causal_mask_function
+    packed_ids = None
     if mask_function is not None and mask_function is not causal_mask_function:
-        raise NotImplementedError("smt_flash attention: custom / packed-sequence masks are not supported")
+        packed_ids = _packed_sequence_ids(mask_function)
+        if packed_ids is None:
+            raise NotImplementedError("smt_flash attention: custom mask functions are not supported (causal, or "
+                                      "causal AND transformers' packed-sequence mask)")
     if q_offset or kv_offset or q_length != kv_length:
         raise NotImplementedError("smt_flash attention: training-style self-attention only (no KV cache)")
+    if packed_ids is not None:
+        if attention_mask is not None:
+            raise NotImplementedError(_DOC_AND_KEY_MASK)
+        if packed_ids.shape != (batch_size, kv_length):
+            raise NotImplementedError(f"smt_flash attention: packed-sequence ids of shape {tuple(packed_ids.shape)} for "
+                                      f"a [{batch_size}, {kv_length}] batch")
+        return DocMask.from_sequence_ids(packed_ids)
     if attention_mask is None:
         return None
     am = attention_mask
