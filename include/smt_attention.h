@@ -1,6 +1,7 @@
 /*
  * smt_attention.h — C-ABI of the gfx950 causal flash attention (forward + backward) used by the SMT
- * training step (csrc/attn_kernels.hip, same library libsmt_hip.so).
+ * training step, and of the split-KV cached forward that serves generation from a KV cache on the
+ * same model (smt_attn_fwd_cached, at the end) (csrc/attn_kernels.hip, same library libsmt_hip.so).
  *
  * Auxiliary to the SMT hot path (smt_hip.h): it replaces the attention of the HF transformers LLaMA
  * decoder that carries the SMT modules (the reference trains that model through
@@ -145,6 +146,43 @@ int smt_attn_bwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const 
                       const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
                       const int32_t* doc_start, const int32_t* doc_end, float p, const uint64_t* seed,
                       const smt_attn_shape* shape, hipStream_t stream);
+
+/*
+ * Cached (KV-cache) forward for inference (additive entry points; the ABI version is unchanged; no
+ * backward). Sq query positions against Skv = shape->S key slots:
+ *   q, o     element (b, h, i, d), h < Hq, i < Sq; k, v element (b, h, j, d), h < Hkv, j < Skv, any
+ *            element strides (a slice of a larger cache buffer, a [B, S, H, D]-ordered cache)
+ *   lse      fp32 [B][Hq][Sq] in the log2 units above, or NULL
+ *   key_mask over the Skv keys, key_mask_ld >= ceil(Skv / 64), or NULL
+ * Query i sits at absolute position q_offset + i and sees key j iff j <= q_offset + i, j < Skv and key
+ * j's mask bit is set. Skv is arbitrary (no % 4, no % 64); q_offset + Sq <= Skv, and Skv may be larger
+ * (a pre-allocated cache): K / V rows at j >= q_offset + Sq are never read, whatever they hold. Rows a
+ * column does not see leave by selection, so an Inf or NaN in a key-masked row does not reach o. A
+ * query whose visible keys are all masked gets o = 0 and lse = +inf, as in smt_attn_fwd_kmask.
+ *
+ * The kernel packs the (query position, query head of one KV head) pairs into the 32 columns of its
+ * matrix products, so the G = Hq / Hkv heads of a group share ONE read of that head's K / V; Sq * G >
+ * 32 takes further column blocks (correct for any Sq, fast for Sq * G <= 32). The keys [0, q_offset +
+ * Sq) are cut into num_splits contiguous ranges of 64-key tiles, one workgroup each per (column block,
+ * b, kv head); with num_splits > 1 each writes fp32 partials (unnormalised O, running max, running
+ * sum) to `workspace` and a second kernel combines them in split order: no atomics, and for a given
+ * num_splits the result is bit-reproducible. A split without a visible key contributes nothing.
+ * num_splits == 1 writes o directly and needs no workspace. num_splits == 0 takes
+ * smt_attn_cached_splits(shape, Sq), a pure host function of (B, Hkv, G, Sq, Skv): >= 1, at most the
+ * number of 64-key tiles of Skv, 1 for Skv <= 64. smt_attn_cached_workspace: the bytes of `workspace`
+ * (16-byte aligned device memory) for num_splits (0 = the default count); 0 when none is needed.
+ * Both return -1 for a bad shape, Sq < 1 or num_splits < 0.
+ *
+ * Returns -1 before any HIP call for a null shape / tensor, Sq < 1, q_offset < 0, q_offset + Sq > Skv
+ * (a query with no key slot of its own), num_splits < 0, a null workspace when one is needed, a dtype
+ * that is not a 16-bit format, Hq % Hkv != 0.
+ */
+int     smt_attn_cached_splits(const smt_attn_shape* shape /* S = Skv */, int32_t Sq);
+int64_t smt_attn_cached_workspace(const smt_attn_shape* shape, int32_t Sq, int32_t num_splits);
+int     smt_attn_fwd_cached(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                            const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
+                            int32_t Sq, int32_t q_offset, int32_t num_splits, void* workspace,
+                            const smt_attn_shape* shape, hipStream_t stream);
 
 #ifdef __cplusplus
 }

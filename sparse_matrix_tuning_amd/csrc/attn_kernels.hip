@@ -1,7 +1,8 @@
 // Causal grouped-query flash attention for gfx950 (CDNA4), head_dim 128, bf16 or fp16 I/O (the model's
 // dtype, smt_attn_shape.dtype; ABI v13), fp32 softmax, optional attention dropout inside the three
 // kernels (DROP instances, smt_attn_*_dropout), optional document mask of packed rows (DOC instances,
-// smt_attn_*_docs).
+// smt_attn_*_docs); and the forward-only split-KV kernel of calls against a KV cache (attn_decode_kernel,
+// smt_attn_fwd_cached).
 // C ABI: include/smt_attention.h. Replaces transformers' sdpa attention (aotriton on this torch
 // build) in the LLaMA decoder that carries the SMT modules.
 //
@@ -1318,6 +1319,224 @@ void attn_dropout_mask_kernel(uint8_t* keep, DropArgs drop, int S, int64_t n_wor
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Cached (KV-cache) forward, smt_attn_fwd_cached: Sq query positions at absolute positions
+// q_offset + i against keys [0, Skv); query i sees key j iff j <= q_offset + i (and j's mask bit).
+// Bound by reading K/V once, so the 32 MFMA columns of S^T[key][col] = K Q^T are (query position,
+// head within the KV group) pairs, col = i * G + g: all G query heads of a KV head ride on one read of
+// its K/V. A workgroup is ONE wave: column block x split x (b, kv head). It sweeps the split's
+// contiguous range of 64-key tiles through the forward's 2-slot LDS ring (2 workgroups = 128 KiB of
+// landing buffers per CU; the tile after the one being computed is in flight) and keeps the forward's
+// lane maps, swizzle and deferred running max. K/V rows at or past the column block's last visible key
+// + 1 are outside the buffer descriptors: never read, zeros in LDS. With a key mask, the V rows of
+// masked keys are zeroed in LDS, so nothing from a row no column sees reaches the P V product.
+// num_splits > 1: fp32 partials per (b*Hkv, column block, split), O [32 col][128 d] then {max, sum}
+// [32 col][2]; attn_decode_combine_kernel merges them in split order (no atomics). A split without a
+// visible key writes max = -inf, sum = 0 and no O; the combine selects such splits out.
+// ------------------------------------------------------------------------------------------------
+constexpr int kDecCols = 32;
+constexpr int kDecPartial = kDecCols * (kD + 2);           // floats per (b*Hkv, column block, split)
+
+struct DecArgs {
+    Tns q, k, v;
+    uint16_t* o;
+    int64_t o_sb, o_sh, o_ss;
+    float* lse;                            // [B][Hq][Sq] or null
+    const uint64_t* kmask;
+    int64_t kmask_ld;
+    float* ws;
+    int Hq, Hkv, G, Sq, q_offset, ncols, ncb, nsplit, tps;     // ncols = Sq * G; tps = tiles per split
+    float sl2;
+};
+
+__device__ __forceinline__ float* dec_ws_o(const DecArgs& a, int64_t slot, int col) {
+    return a.ws + (slot * kDecCols + col) * kD;
+}
+__device__ __forceinline__ float* dec_ws_ml(const DecArgs& a, int64_t nslots, int64_t slot, int col) {
+    return a.ws + nslots * kDecCols * kD + (slot * kDecCols + col) * 2;
+}
+
+template <bool KMASK, int F, bool DIRECT>
+__global__ __launch_bounds__(64)
+void attn_decode_kernel(DecArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // K/V ring: 2 x 32 KiB
+    const int cb = blockIdx.x, sp = blockIdx.y, bh = blockIdx.z;
+    const int b = bh / a.Hkv, hk = bh - b * a.Hkv;
+    const int lane = threadIdx.x, hi = lane >> 5, l32 = lane & 31;
+    const int col = cb * kDecCols + l32;
+    const bool cvalid = col < a.ncols;
+    const int qi = cvalid ? col / a.G : 0;
+    const int h = hk * a.G + (cvalid ? col - qi * a.G : 0);
+    const int qpos = cvalid ? a.q_offset + qi : -1;            // an unused column sees no key
+    // keys this column block can see: [0, kv_end), kv_end <= Skv (checked by the host)
+    const int kv_end = a.q_offset + min(a.Sq - 1, (cb * kDecCols + kDecCols - 1) / a.G) + 1;
+    const int t0 = sp * a.tps, t1 = min((kv_end + kKV - 1) / kKV, t0 + a.tps);
+    const int64_t nslots = (int64_t)gridDim.z * a.ncb * a.nsplit;
+    const int64_t slot = ((int64_t)bh * a.ncb + cb) * a.nsplit + sp;
+    if (t0 >= t1) {                                            // an empty split (never with DIRECT)
+        if (!DIRECT && cvalid && hi == 0) {
+            float* ml = dec_ws_ml(a, nslots, slot, l32);
+            ml[0] = kNegInf;
+            ml[1] = 0.f;
+        }
+        return;
+    }
+    const uint16_t* qp = a.q.p + b * a.q.sb + h * a.q.sh + (int64_t)qi * a.q.ss;
+    const uint16_t* kp = a.k.p + b * a.k.sb + hk * a.k.sh;
+    const uint16_t* vp = a.v.p + b * a.v.sb + hk * a.v.sh;
+    const uint64_t* km = KMASK ? a.kmask + (int64_t)b * a.kmask_ld : nullptr;
+    bf16x8_t qf[8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+        if (cvalid) qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + 16 * ks + 8 * hi);
+        else qf[ks] = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
+    }
+    // the descriptors end with row kv_end - 1: later rows are never read (they land as zeros)
+    const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(kp, (int64_t)(kv_end - 1) * a.k.ss * 2 + kRowB);
+    const __amdgpu_buffer_rsrc_t rv = uniform_rsrc(vp, (int64_t)(kv_end - 1) * a.v.ss * 2 + kRowB);
+    const uint32_t lds0 = lds_addr(lds);
+    const TrLane tl = tr_lane(lane);
+    f32x16_t o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[dt][i] = 0.f;
+    float m_run = kNegInf, l_run = 0.f;
+
+    auto issue = [&](int t) {                                  // K(t), V(t) into slot t & 1
+        const uint32_t s = lds0 + (uint32_t)((t & 1) * 2 * kTileB);
+        dma_rows(rk, a.k.ss, s, t * kKV, t * kKV, kKV / 4, lane);
+        dma_rows(rv, a.v.ss, s + kTileB, t * kKV, t * kKV, kKV / 4, lane);
+    };
+    issue(t0);
+    vm_wait_all();
+    vm_wait_all_known();                                       // the Q fragments too (compiler-visible)
+    __syncthreads();
+    for (int t = t0; t < t1; ++t) {
+        if (t + 1 < t1) issue(t + 1);
+        uint8_t* K = lds + (t & 1) * 2 * kTileB;
+        uint8_t* V = K + kTileB;
+        const int k0 = t * kKV;
+        uint64_t w = ~0ull;
+        if (KMASK) {
+            w = km[t];                                         // workgroup-uniform
+            if (~w != 0ull) {
+                if (!key_bit(w, lane)) {                       // lane = the tile's row: a masked key's V row
+#pragma unroll
+                    for (int c = 0; c < 16; ++c) *reinterpret_cast<u32x4_t*>(V + lane * kRowB + 16 * c) = u32x4_t{0u, 0u, 0u, 0u};
+                }
+                __syncthreads();
+            }
+        }
+        f32x16_t sc[2];
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                sc[j] = mfma<F>(row_frag(K, 32 * j + l32, 32 * ks + 16 * hi), qf[ks], ks ? sc[j] : f32x16_t{});
+        float x[32];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) x[16 * j + i] = sc[j][i];
+        // hidden keys leave by selection: the causal edge (which covers the ragged end, qpos < kv_end)
+        // and the key mask
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const int key = k0 + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * hi;
+            if (key > qpos || (KMASK && !key_bit(w, key))) x[i] = kNegInf;
+        }
+        float mx = x[0];
+#pragma unroll
+        for (int i = 1; i < 32; ++i) mx = fmaxf(mx, x[i]);
+        const float m_tile = other_half_max(mx) * a.sl2;
+        const bool move = m_tile > m_run + kFwdThr;
+        const float m_new = move ? m_tile : m_run;
+        const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.f;
+        const float m_use = (m_new == kNegInf) ? 0.f : m_new;
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[i], a.sl2, -m_use));
+            sum += x[i];
+        }
+        l_run = l_run * alpha + sum;
+        m_run = m_new;
+        if (__builtin_amdgcn_ballot_w64(move) != 0) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
+        }
+        bf16x8_t pf[4];
+        pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[0]), pf[0], pf[1]);
+        pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[16]), pf[2], pf[3]);
+#pragma unroll
+        for (int n = 0; n < 16; ++n) o[n >> 2] = mfma<F>(tr_frag(V, tl, 16 * (n & 3), 32 * (n >> 2)), pf[n & 3], o[n >> 2]);
+        vm_wait_all();
+        __syncthreads();
+    }
+    const float l_tot = halves_sum(l_run);
+    if (!cvalid) return;
+    if (DIRECT) {
+        const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+        uint16_t* op = a.o + b * a.o_sb + h * a.o_sh + (int64_t)qi * a.o_ss;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                uint2 wd;
+                wd.x = pk16<F>(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv);
+                wd.y = pk16<F>(o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
+                *reinterpret_cast<uint2*>(op + 32 * dt + 8 * g + 4 * hi) = wd;
+            }
+        if (a.lse && hi == 0)
+            a.lse[((int64_t)b * a.Hq + h) * a.Sq + qi] = l_tot > 0.f ? m_run + __log2f(l_tot) : __builtin_huge_valf();
+    } else {
+        const bool any = l_tot > 0.f;
+        if (any) {
+            float* po = dec_ws_o(a, slot, l32);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(po + 32 * dt + 8 * g + 4 * hi) =
+                        float4{o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
+        }
+        if (hi == 0) {
+            float* ml = dec_ws_ml(a, nslots, slot, l32);
+            ml[0] = any ? m_run : kNegInf;
+            ml[1] = any ? l_tot : 0.f;
+        }
+    }
+}
+
+// One workgroup per (column, b*Hkv), one thread per d: the splits' partials in split order.
+template <int F>
+__global__ __launch_bounds__(kD)
+void attn_decode_combine_kernel(DecArgs a) {
+    const int col = blockIdx.x, bh = blockIdx.y, d = threadIdx.x;
+    const int b = bh / a.Hkv, hk = bh - b * a.Hkv;
+    const int cb = col / kDecCols, c = col - cb * kDecCols;
+    const int qi = col / a.G, h = hk * a.G + (col - qi * a.G);
+    const int64_t nslots = (int64_t)gridDim.y * a.ncb * a.nsplit;
+    const int64_t slot0 = ((int64_t)bh * a.ncb + cb) * a.nsplit;
+    float M = kNegInf;
+    for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, dec_ws_ml(a, nslots, slot0 + s, c)[0]);
+    float L = 0.f, acc = 0.f;
+    for (int s = 0; s < a.nsplit; ++s) {
+        const float* ml = dec_ws_ml(a, nslots, slot0 + s, c);
+        if (ml[0] == kNegInf) continue;                        // no visible key in this split: its O was not written
+        const float wgt = __builtin_amdgcn_exp2f(ml[0] - M);
+        L = __builtin_fmaf(wgt, ml[1], L);
+        acc = __builtin_fmaf(wgt, dec_ws_o(a, slot0 + s, c)[d], acc);
+    }
+    const bool any = L > 0.f;
+    const uint32_t r = pk16<F>(any ? acc / L : 0.f, 0.f);
+    a.o[b * a.o_sb + h * a.o_sh + (int64_t)qi * a.o_ss + d] = (uint16_t)(r & 0xffffu);
+    if (a.lse && d == 0) a.lse[((int64_t)b * a.Hq + h) * a.Sq + qi] = any ? M + __log2f(L) : __builtin_huge_valf();
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int check_tensor(const smt_attn_tensor* t, const char* what, const char* fn) {
@@ -1475,6 +1694,39 @@ int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
 
 constexpr DropArgs kNoDrop = {nullptr, 0u, 1.f};
 
+// Cached forward: column blocks of a call, and the default split count. Host arithmetic only.
+int dec_col_blocks(const smt_attn_shape* s, int32_t Sq) {
+    return (int)(((int64_t)Sq * (s->Hq / s->Hkv) + kDecCols - 1) / kDecCols);
+}
+
+// Workgroups are one wave with a 64 KiB ring, two per CU: 512 run at once on the 256 CUs. Split until
+// the grid has that many, but never below kDecMinTiles tiles per split (a split's fixed cost: the Q
+// load, a first tile nothing overlaps, its partials and their combine).
+constexpr int kDecWgSlots = 512, kDecMinTiles = 2;
+int dec_default_splits(const smt_attn_shape* s, int32_t Sq) {
+    const int64_t base = (int64_t)s->B * s->Hkv * dec_col_blocks(s, Sq);
+    const int64_t tiles = ((int64_t)s->S + kKV - 1) / kKV;
+    int64_t n = (kDecWgSlots + base - 1) / base;
+    if (n > tiles / kDecMinTiles) n = tiles / kDecMinTiles;
+    return n < 1 ? 1 : (int)n;
+}
+
+int64_t dec_workspace(const smt_attn_shape* s, int32_t Sq, int32_t num_splits) {
+    if (num_splits <= 1) return 0;
+    return (int64_t)s->B * s->Hkv * dec_col_blocks(s, Sq) * num_splits * kDecPartial * (int64_t)sizeof(float);
+}
+
+#define SMT_ATTN_LAUNCH_DEC(F, kmask, direct, grid, stream, args)                                                \
+    do {                                                                                                      \
+        if (kmask) {                                                                                          \
+            if (direct) hipLaunchKernelGGL((attn_decode_kernel<true, F, true>), grid, dim3(64), 0, stream, args);  \
+            else hipLaunchKernelGGL((attn_decode_kernel<true, F, false>), grid, dim3(64), 0, stream, args);   \
+        } else {                                                                                              \
+            if (direct) hipLaunchKernelGGL((attn_decode_kernel<false, F, true>), grid, dim3(64), 0, stream, args); \
+            else hipLaunchKernelGGL((attn_decode_kernel<false, F, false>), grid, dim3(64), 0, stream, args);  \
+        }                                                                                                     \
+    } while (0)
+
 }  // namespace
 
 extern "C" {
@@ -1583,6 +1835,74 @@ int smt_attn_dropout_mask(uint8_t* keep, float p, const uint64_t* seed, const sm
     if (blocks > 0x7fffffffLL) return fail(-1, "%s: too many blocks", fn);
     hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, keep, drop, shape->S, n_words);
     return check_launch("attn_dropout_mask_kernel");
+}
+
+int smt_attn_cached_splits(const smt_attn_shape* shape, int32_t Sq) {
+    const char* fn = "smt_attn_cached_splits";
+    int rc;
+    if ((rc = check_shape(shape, fn))) return rc;
+    if (Sq < 1) return fail(-1, "%s: Sq = %d", fn, (int)Sq);
+    return dec_default_splits(shape, Sq);
+}
+
+int64_t smt_attn_cached_workspace(const smt_attn_shape* shape, int32_t Sq, int32_t num_splits) {
+    const char* fn = "smt_attn_cached_workspace";
+    int rc;
+    if ((rc = check_shape(shape, fn))) return rc;
+    if (Sq < 1 || num_splits < 0) return fail(-1, "%s: Sq = %d, num_splits = %d", fn, (int)Sq, (int)num_splits);
+    return dec_workspace(shape, Sq, num_splits ? num_splits : dec_default_splits(shape, Sq));
+}
+
+int smt_attn_fwd_cached(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                        const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
+                        int32_t Sq, int32_t q_offset, int32_t num_splits, void* workspace,
+                        const smt_attn_shape* shape, hipStream_t stream) {
+    const char* fn = "smt_attn_fwd_cached";
+    int rc;
+    if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
+        (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)))
+        return rc;
+    const int Skv = shape->S;
+    if (Sq < 1) return fail(-1, "%s: Sq = %d (at least one query position)", fn, (int)Sq);
+    if (q_offset < 0) return fail(-1, "%s: q_offset = %d is negative", fn, (int)q_offset);
+    if ((int64_t)q_offset + Sq > Skv)
+        return fail(-1, "%s: q_offset %d + Sq %d > Skv %d (a query without a key slot of its own)", fn, (int)q_offset,
+                    (int)Sq, Skv);
+    if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
+    if (key_mask && key_mask_ld < (Skv + 63) / 64)
+        return fail(-1, "%s: key_mask_ld %lld < ceil(Skv / 64)", fn, (long long)key_mask_ld);
+    const int nsplit = num_splits ? num_splits : dec_default_splits(shape, Sq);
+    if (nsplit > 65535) return fail(-1, "%s: num_splits = %d is above 65535", fn, nsplit);
+    if (nsplit > 1 && !workspace)
+        return fail(-1, "%s: null workspace with %d splits (smt_attn_cached_workspace bytes)", fn, nsplit);
+    if (nsplit > 1 && !al16(workspace)) return fail(-2, "%s: workspace needs 16-byte alignment", fn);
+    const int kv_all = q_offset + Sq;                      // keys any query of the call sees: [0, kv_all)
+    if ((int64_t)kv_all * k->ss * 2 >= 0x7fffffffLL || (int64_t)kv_all * v->ss * 2 >= 0x7fffffffLL)
+        return fail(-2, "%s: the visible K / V rows of one head must span less than 2 GiB", fn);
+    const int64_t ncols = (int64_t)Sq * (shape->Hq / shape->Hkv);
+    const int64_t bh = (int64_t)shape->B * shape->Hkv;
+    if (ncols > 0x7fffffffLL / 2 || bh > 65535) return fail(-1, "%s: B * Hkv must stay within 65535 and Sq * G below 2^30", fn);
+    DecArgs a;
+    a.q = tns(q); a.k = tns(k); a.v = tns(v);
+    a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o->sb; a.o_sh = o->sh; a.o_ss = o->ss;
+    a.lse = lse;
+    a.kmask = key_mask; a.kmask_ld = key_mask_ld;
+    a.ws = static_cast<float*>(workspace);
+    a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.G = shape->Hq / shape->Hkv;
+    a.Sq = Sq; a.q_offset = q_offset;
+    a.ncols = (int)ncols; a.ncb = dec_col_blocks(shape, Sq); a.nsplit = nsplit;
+    const int tiles = (kv_all + kKV - 1) / kKV;
+    a.tps = (tiles + nsplit - 1) / nsplit;
+    a.sl2 = shape->scale * 1.4426950408889634f;
+    const dim3 grid((unsigned)a.ncb, (unsigned)nsplit, (unsigned)bh);
+    if (shape->dtype == SMT_DTYPE_FP16) SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_FP16, key_mask, nsplit == 1, grid, stream, a);
+    else SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_BF16, key_mask, nsplit == 1, grid, stream, a);
+    if ((rc = check_launch("attn_decode_kernel")) || nsplit == 1) return rc;
+    const dim3 cgrid((unsigned)ncols, (unsigned)bh);
+    if (shape->dtype == SMT_DTYPE_FP16)
+        hipLaunchKernelGGL(attn_decode_combine_kernel<SMT_DTYPE_FP16>, cgrid, dim3(kD), 0, stream, a);
+    else hipLaunchKernelGGL(attn_decode_combine_kernel<SMT_DTYPE_BF16>, cgrid, dim3(kD), 0, stream, a);
+    return check_launch("attn_decode_combine_kernel");
 }
 
 }  // extern "C"

@@ -11,7 +11,9 @@ match the eager model up to reduction order / exp ulps (tests/test_gpu_fused_lla
 It also routes the decoder's attention to a gfx950 causal flash attention (forward + backward,
 ``csrc/attn_kernels.hip``, C ABI ``include/smt_attention.h``), registered with transformers'
 ``AttentionInterface`` as ``"smt_flash"``; sdpa on this torch build runs aotriton at 25-27 % of the
-step. Tolerances vs an fp32 reference are in tests/test_gpu_attention.py.
+step. Tolerances vs an fp32 reference are in tests/test_gpu_attention.py. Calls against a KV cache
+(``generate()`` on the patched model) run a split-KV decode kernel, forward only
+(:func:`flash_attention_cached`, tests/test_gpu_attention_cached.py, tests/test_gpu_generate.py).
 
 The causal-LM loss (transformers ``ForCausalLMLoss``: ``logits.float()`` then cross entropy) becomes
 two row kernels over the bf16 logits (``smt_ce_fwd`` / ``smt_ce_bwd``), so the 16.8 GB fp32 logits
@@ -1031,22 +1033,118 @@ def flash_attention(q, k, v, scale=None, key_mask: "KeyMask" = None, joint: bool
                              dropout_p, seed, doc_mask)
 
 
+class CacheMask:
+    """What :func:`smt_flash_mask` returns for a call against a KV cache: ``key_mask`` (a
+    :class:`KeyMask` over the ``kv_length`` cached keys, or None), the absolute position ``q_offset``
+    of the call's first query and ``kv_length``."""
+
+    __slots__ = ("key_mask", "q_offset", "kv_length")
+
+    def __init__(self, key_mask, q_offset: int, kv_length: int):
+        self.key_mask, self.q_offset, self.kv_length = key_mask, int(q_offset), int(kv_length)
+
+
+def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_offset: int = None,
+                           num_splits: int = None, return_lse: bool = False):
+    """Attention of ``Sq`` new positions against a KV cache, forward only (``smt_attn_fwd_cached``, the
+    split-KV decode kernel): q ``[B, Hq, Sq, 128]``, k / v ``[B, Hkv, Skv, 128]`` (any strides with
+    head_dim innermost: a slice of a pre-allocated buffer, a ``[B, S, H, D]``-ordered cache) ->
+    ``[B, Sq, Hq, 128]``. Query i sits at position ``q_offset + i`` (default ``Skv - Sq``: the queries
+    are the last positions) and sees key j iff ``j <= q_offset + i`` and ``key_mask`` (over the Skv
+    keys) keeps j; K / V rows at ``q_offset + Sq`` and later are never read. Any ``Skv``.
+    ``num_splits``: how many workgroups share one (batch, kv head)'s key range (None: the library's
+    default for the shape); the result is bit-reproducible for a given value. ``return_lse``: also
+    return the fp32 ``[B, Hq, Sq]`` log-sum-exp (log2 units, include/smt_attention.h). The workspace
+    comes from torch's allocator; nothing synchronises with the host. There is no backward: an input
+    that requires grad while gradients are enabled raises."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise NotImplementedError("flash_attention_cached: cached attention has no backward (inference only); run "
+                                  "under torch.no_grad() or detach the inputs")
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _need(t, "cached flash attention " + n, like=q)
+    if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape:
+        raise NotImplementedError(f"cached flash attention: 4-D q, k, v (q {tuple(q.shape)}, k {tuple(k.shape)}, "
+                                  f"v {tuple(v.shape)})")
+    B, Hq, Sq, D = q.shape
+    Hkv, Skv = k.shape[1], k.shape[2]
+    if D != 128 or k.shape != (B, Hkv, Skv, D) or Hq % Hkv or Sq < 1:
+        raise NotImplementedError(f"cached flash attention: head_dim 128, Hq % Hkv == 0, Sq >= 1 "
+                                  f"(q {tuple(q.shape)}, k {tuple(k.shape)})")
+    q_offset = Skv - Sq if q_offset is None else int(q_offset)
+    if q_offset < 0 or q_offset + Sq > Skv:
+        raise ValueError(f"cached flash attention: queries at positions [{q_offset}, {q_offset + Sq}) of {Skv} key slots")
+    num_splits = 0 if num_splits is None else int(num_splits)
+    if num_splits < 0:
+        raise ValueError(f"cached flash attention: num_splits = {num_splits}")
+    q, k, v = _attn_ready(q), _attn_ready(k), _attn_ready(v)
+    for t in (k, v):
+        if Skv * t.stride(2) * 2 >= 2 ** 31:
+            raise NotImplementedError("cached flash attention: per-head extent must stay below 2 GiB")
+    km, km_ld = None, 0
+    if key_mask is not None:
+        if key_mask.S != Skv or key_mask.bits.shape[0] != B or key_mask.bits.device != q.device:
+            raise ValueError(f"cached flash attention: key mask for [{key_mask.bits.shape[0]}, {key_mask.S}] keys, "
+                             f"cache has [{B}, {Skv}]")
+        km, km_ld = key_mask.bits.data_ptr(), key_mask.bits.shape[1]
+    o = torch.empty(B, Sq, Hq, D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, Hq, Sq, dtype=torch.float32, device=q.device) if return_lse else None
+    shape = _hip.AttnShape(B, Hq, Hkv, Skv, float(scale if scale is not None else D ** -0.5), _dt(q))
+    lib = _hip.load()
+    if num_splits == 0:
+        num_splits = lib.smt_attn_cached_splits(ctypes.byref(shape), Sq)
+        _hip._check(min(num_splits, 0), "smt_attn_cached_splits")
+    ws_bytes = lib.smt_attn_cached_workspace(ctypes.byref(shape), Sq, num_splits)
+    _hip._check(min(ws_bytes, 0), "smt_attn_cached_workspace")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes else None
+    with torch.cuda.device(q.device):
+        rc = lib.smt_attn_fwd_cached(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
+                                     ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(o.transpose(1, 2))),
+                                     lse.data_ptr() if lse is not None else None, km, km_ld, Sq, q_offset, num_splits,
+                                     ws.data_ptr() if ws is not None else None, ctypes.byref(shape), _stream(q))
+    _hip._check(rc, "smt_attn_fwd_cached")
+    return (o, lse) if return_lse else o
+
+
 def smt_flash_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None,
                                 is_causal=None, **kwargs):
     """transformers attention-function signature (``AttentionInterface``). Causal self-attention,
     unpadded (``attention_mask`` None), padded (a :class:`KeyMask` from :func:`smt_flash_mask`) or
     packed (a :class:`DocMask` from :func:`smt_flash_mask` or built by the caller);
     ``dropout`` (transformers passes the config's ``attention_dropout`` in training mode, 0.0 in eval)
-    runs inside the kernels; anything else raises rather than silently changing semantics."""
-    if attention_mask is not None and not isinstance(attention_mask, (KeyMask, DocMask)):
+    runs inside the kernels; anything else raises rather than silently changing semantics.
+
+    A call against a KV cache (a :class:`CacheMask` from :func:`smt_flash_mask`, or fewer queries than
+    keys) runs :func:`flash_attention_cached`, forward only: dropout or a :class:`DocMask` with a
+    cache raises. So does a same-length call whose length is not a multiple of 4 when it needs no
+    gradient (the prefill of an odd-length prompt; the training kernels need ``S % 4 == 0``). Every
+    other same-length call goes to :func:`flash_attention` as before."""
+    if attention_mask is not None and not isinstance(attention_mask, (KeyMask, DocMask, CacheMask)):
         raise NotImplementedError("smt_flash attention: only key-padding and document masks built by smt_flash_mask "
                                   f"are supported (got {type(attention_mask).__name__})")
     if is_causal is False or not getattr(module, "is_causal", True):
         raise NotImplementedError("smt_flash attention: causal attention only")
+    Sq, Skv = query.shape[2], key.shape[2]
+    cached = isinstance(attention_mask, CacheMask) or Sq != Skv
+    dropout = float(dropout or 0.0)
+    if cached:
+        if dropout != 0.0:
+            raise NotImplementedError("smt_flash attention: dropout with a KV cache (the cached kernel is inference only)")
+        if isinstance(attention_mask, DocMask):
+            raise NotImplementedError("smt_flash attention: packed rows (a document mask) with a KV cache")
+        km, q_offset = attention_mask, None
+        if isinstance(attention_mask, CacheMask):
+            if attention_mask.kv_length != Skv:
+                raise ValueError(f"smt_flash attention: mask built for {attention_mask.kv_length} cached keys, the "
+                                 f"cache holds {Skv}")
+            km, q_offset = attention_mask.key_mask, attention_mask.q_offset
+        return flash_attention_cached(query, key, value, scaling, km, q_offset), None
+    if (Sq % 4 and dropout == 0.0 and not isinstance(attention_mask, DocMask)
+            and not (torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad))):
+        return flash_attention_cached(query, key, value, scaling, attention_mask, 0), None
     # the engine marks attention modules whose q/k/v_proj share a joint transposed copy
     docs = attention_mask if isinstance(attention_mask, DocMask) else None
     return flash_attention(query, key, value, scaling, None if docs is not None else attention_mask,
-                           joint=getattr(module, "_smt_joint_qkv_grad", False), dropout_p=float(dropout or 0.0),
+                           joint=getattr(module, "_smt_joint_qkv_grad", False), dropout_p=dropout,
                            doc_mask=docs), None
 
 
@@ -1085,8 +1183,14 @@ def smt_flash_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mas
     one: the causal mask AND the 2-D padding mask, exactly the mask ``sdpa_mask`` would materialise
     as [B, 1, S, S]; a :class:`DocMask` for a packed batch (restarting ``position_ids`` and no
     ``attention_mask``: transformers hands over causal AND ``packed_sequence_mask_function(ids)``).
-    Anything the kernels do not implement (a KV cache / offsets, sliding windows, custom mask
-    functions) raises."""
+    A call against a KV cache (``q_length != kv_length`` or ``q_offset != 0``: the decode steps of
+    ``generate()`` with the default ``DynamicCache``) gets a :class:`CacheMask`: the offset, the cache
+    length and the 2-D ``attention_mask`` (of a left-padded batch) as a :class:`KeyMask` over the
+    ``kv_length`` keys, built without a host synchronisation (nothing asks whether every key is valid:
+    this runs once per generated token).
+    Anything the kernels do not implement (``kv_offset != 0``, sliding windows, custom mask
+    functions, packed rows together with a cache, a tensor-valued ``q_offset`` of a static cache
+    under ``torch.compile``) raises."""
     from transformers.masking_utils import causal_mask_function
     packed_ids = None
     if mask_function is not None and mask_function is not causal_mask_function:
@@ -1094,8 +1198,24 @@ def smt_flash_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mas
         if packed_ids is None:
             raise NotImplementedError("smt_flash attention: custom mask functions are not supported (causal, or "
                                       "causal AND transformers' packed-sequence mask)")
-    if q_offset or kv_offset or q_length != kv_length:
-        raise NotImplementedError("smt_flash attention: training-style self-attention only (no KV cache)")
+    if isinstance(q_offset, torch.Tensor) or isinstance(kv_offset, torch.Tensor):
+        raise NotImplementedError("smt_flash attention: tensor-valued cache offsets (a static cache under "
+                                  "torch.compile) are not supported; use the default DynamicCache")
+    if kv_offset:
+        raise NotImplementedError("smt_flash attention: kv_offset != 0 (a sliding or offset cache) is not supported")
+    if q_offset or q_length != kv_length:
+        if packed_ids is not None:
+            raise NotImplementedError("smt_flash attention: packed rows together with a KV cache are not supported")
+        if q_offset < 0 or q_offset + q_length > kv_length:
+            raise NotImplementedError(f"smt_flash attention: queries [{q_offset}, {q_offset + q_length}) do not fit "
+                                      f"{kv_length} cached keys")
+        km = None
+        if attention_mask is not None:
+            am = attention_mask
+            if am.dim() != 2 or am.shape[0] != batch_size or am.shape[1] < kv_length:
+                raise NotImplementedError(f"smt_flash attention: 2-D [B, S] padding mask expected, got {tuple(am.shape)}")
+            km = KeyMask.from_padding_mask(am[:, :kv_length])
+        return CacheMask(km, q_offset, kv_length)
     if packed_ids is not None:
         if attention_mask is not None:
             raise NotImplementedError(_DOC_AND_KEY_MASK)
