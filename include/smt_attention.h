@@ -148,6 +148,34 @@ int smt_attn_bwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const 
                       const smt_attn_shape* shape, hipStream_t stream);
 
 /*
+ * Any sequence length (additive entry points; the ABI version is unchanged): the general form of the
+ * chain above, with a row stride of their own for lse and delta. lse and delta_ws are fp32
+ * [B][Hq][lse_ld] with lse_ld >= S, lse_ld % 4 == 0 and 16-byte aligned base pointers; S >= 1 is
+ * otherwise free (the dK / dV kernel fetches lse and delta in 16-byte groups, so it is their rows that
+ * need the alignment, not S). The forward writes entries [0, S) of each row and does not touch
+ * [S, lse_ld). The backward's results do not depend on what [S, lse_ld) holds in lse or in delta_ws:
+ * any bit pattern, NaN and Inf included (those entries are never fetched: the buffer descriptor of the
+ * dK / dV kernel's 16-byte fetch ends at entry S of the row, its range check is per dword, and the
+ * entries past S land as zeros). key_mask, doc_start / doc_end, p and seed mean what they mean above: key_mask NULL = no key
+ * mask, both doc arrays NULL = no documents, t == 0 = no dropout (seed may then be NULL); the keep
+ * function does not depend on S or lse_ld. Every entry point above is this one with lse_ld = S (so
+ * smt_attn_bwd* still returns -2 for S % 4 != 0).
+ *
+ * Returns -1 before any HIP call for lse_ld < S, lse_ld % 4 != 0, exactly one doc array NULL, a key
+ * mask together with documents, p outside [0, 1), a NULL seed with t > 0, and the null or malformed
+ * arguments the entry points above refuse; -2 for misaligned lse / delta_ws pointers (backward).
+ */
+int smt_attn_fwd_ld(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                    const smt_attn_tensor* o, float* lse, int64_t lse_ld, const uint64_t* key_mask, int64_t key_mask_ld,
+                    const int32_t* doc_start, const int32_t* doc_end, float p, const uint64_t* seed,
+                    const smt_attn_shape* shape, hipStream_t stream);
+int smt_attn_bwd_ld(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                    const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
+                    int64_t lse_ld, const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
+                    const uint64_t* key_mask, int64_t key_mask_ld, const int32_t* doc_start, const int32_t* doc_end,
+                    float p, const uint64_t* seed, const smt_attn_shape* shape, hipStream_t stream);
+
+/*
  * Cached (KV-cache) forward for inference (additive entry points; the ABI version is unchanged; no
  * backward). Sq query positions against Skv = shape->S key slots:
  *   q, o     element (b, h, i, d), h < Hq, i < Sq; k, v element (b, h, j, d), h < Hkv, j < Skv, any

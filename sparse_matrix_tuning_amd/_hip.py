@@ -43,7 +43,7 @@ ABI_FUNCTIONS = (
     "smt_rope_fwd", "smt_rope_bwd", "smt_swiglu_fwd", "smt_swiglu_bwd", "smt_ce_fwd", "smt_ce_bwd",
     "smt_attn_last_error", "smt_attn_fwd", "smt_attn_bwd", "smt_attn_fwd_kmask", "smt_attn_bwd_kmask",
     "smt_attn_dropout_threshold", "smt_attn_fwd_dropout", "smt_attn_bwd_dropout", "smt_attn_dropout_mask",
-    "smt_attn_fwd_docs", "smt_attn_bwd_docs",
+    "smt_attn_fwd_docs", "smt_attn_bwd_docs", "smt_attn_fwd_ld", "smt_attn_bwd_ld",
     "smt_attn_cached_splits", "smt_attn_cached_workspace", "smt_attn_fwd_cached",
     "smt_fp8_last_error", "smt_quant_rows_e4m3", "smt_quant_cols_t_e4m3", "smt_quant_rows_cat_e4m3",
     "smt_swiglu_fwd_quant_e4m3", "smt_swiglu_bwd_quant_e4m3", "smt_swiglu_bwd_quant_e4m3_packed",
@@ -172,6 +172,10 @@ _SIGS = {
                                          ctypes.POINTER(AttnShape), _P]),
     "smt_attn_bwd_docs": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 5 + [_P, _P] + [ctypes.POINTER(AttnTensor)] * 3
                           + [_P, _P, ctypes.c_float, _P, ctypes.POINTER(AttnShape), _P]),
+    "smt_attn_fwd_ld": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 4 + [_P, _I64, _P, _I64, _P, _P, ctypes.c_float, _P,
+                                       ctypes.POINTER(AttnShape), _P]),
+    "smt_attn_bwd_ld": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 5 + [_P, _P, _I64] + [ctypes.POINTER(AttnTensor)] * 3
+                        + [_P, _I64, _P, _P, ctypes.c_float, _P, ctypes.POINTER(AttnShape), _P]),
     "smt_attn_cached_splits": (ctypes.c_int, [ctypes.POINTER(AttnShape), _I32]),
     "smt_attn_cached_workspace": (_I64, [ctypes.POINTER(AttnShape), _I32, _I32]),
     "smt_attn_fwd_cached": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 4 + [_P, _P, _I64, _I32, _I32, _I32, _P,

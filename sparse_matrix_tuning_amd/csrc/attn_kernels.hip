@@ -2,7 +2,10 @@
 // dtype, smt_attn_shape.dtype; ABI v13), fp32 softmax, optional attention dropout inside the three
 // kernels (DROP instances, smt_attn_*_dropout), optional document mask of packed rows (DOC instances,
 // smt_attn_*_docs); and the forward-only split-KV kernel of calls against a KV cache (attn_decode_kernel,
-// smt_attn_fwd_cached).
+// smt_attn_fwd_cached). Any sequence length S >= 1, forward and backward: lse and delta are
+// [B][Hq][lse_ld] with a row stride lse_ld % 4 == 0 of their own (smt_attn_fwd_ld / smt_attn_bwd_ld),
+// which is all the 16-byte lse / delta fetch of the dK/dV kernel needs; the other entry points are
+// these with lse_ld = S.
 // C ABI: include/smt_attention.h. Replaces transformers' sdpa attention (aotriton on this torch
 // build) in the LLaMA decoder that carries the SMT modules.
 //
@@ -330,6 +333,7 @@ struct FwdArgs {
     uint16_t* o;
     int64_t o_sb, o_sh, o_ss;
     float* lse;
+    int lse_ld;                            // row stride of lse: >= S, % 4 == 0
     const uint64_t* kmask;
     int64_t kmask_ld;
     int B, Hq, Hkv, S;
@@ -613,7 +617,7 @@ struct FwdLean {
                     *reinterpret_cast<uint2*>(op + d) = w;
                 }
             if (hi == 0)
-                a.lse[((int64_t)b * a.Hq + h) * a.S + qrow] =
+                a.lse[((int64_t)b * a.Hq + h) * a.lse_ld + qrow] =
                     (KMASK && !(l_tot > 0.f)) ? __builtin_huge_valf() : m_run + __log2f(l_tot);
         }
     }
@@ -669,6 +673,7 @@ struct DqArgs {
     int64_t dq_sb, dq_sh, dq_ss;
     const float* lse;
     float* delta;
+    int lse_ld;                            // row stride of lse and delta
     const uint64_t* kmask;
     int64_t kmask_ld;
     int B, Hq, Hkv, S;
@@ -824,7 +829,7 @@ struct DqLean {
                 df[ks] = qf[ks];
             }
         }
-        const int64_t srow = ((int64_t)b * a.Hq + h) * a.S + (qvalid ? qrow : 0);
+        const int64_t srow = ((int64_t)b * a.Hq + h) * a.lse_ld + (qvalid ? qrow : 0);
         lse = qvalid ? a.lse[srow] : 0.f;
         {
             const uint16_t* op = a.o.p + b * a.o.sb + h * a.o.sh;
@@ -967,6 +972,7 @@ struct DkvArgs {
     int64_t dv_sb, dv_sh, dv_ss;
     const float* lse;
     const float* delta;
+    int lse_ld;                            // row stride of lse and delta: >= S, % 4 == 0
     const uint64_t* kmask;
     int64_t kmask_ld;
     int B, Hq, Hkv, S;
@@ -1035,7 +1041,12 @@ struct DkvLean {
                      s0 + 8 * wave, 2, lane);
         }
         if (wave < 2 && lane < 8) {
-            const float* row = (wave == 0 ? a.lse : a.delta) + ((int64_t)b * a.Hq + h) * a.S;
+            // Rows of lse_ld floats are 16-byte aligned for any S; the descriptor ends at entry S, so the
+            // pad [S, lse_ld) is never fetched, whatever it holds. The range check of buffer_load_dwordx4
+            // is per dword, also with the LDS destination: of the group that straddles S the entries
+            // below S land and the others land as zeros, as every entry of a group past S does
+            // (tests/test_gpu_attention_anylen.py::test_results_do_not_depend_on_the_pad holds NaN there).
+            const float* row = (wave == 0 ? a.lse : a.delta) + ((int64_t)b * a.Hq + h) * a.lse_ld;
             dma16(uniform_rsrc(row, (int64_t)a.S * 4), __builtin_amdgcn_readfirstlane(buf + 2 * kSliceB + 128 * wave),
                   (s0 + 4 * lane) * 4);
         }
@@ -1614,8 +1625,8 @@ constexpr DocArgs kNoDocs = {nullptr, nullptr};
 
 // fn: the entry point's name for messages; drop.t == 0: the plain kernels; docs.start: the DOC kernels
 int attn_fwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
-             const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld, DropArgs drop,
-             DocArgs docs, const smt_attn_shape* shape, hipStream_t stream) {
+             const smt_attn_tensor* o, float* lse, int64_t lse_ld, const uint64_t* key_mask, int64_t key_mask_ld,
+             DropArgs drop, DocArgs docs, const smt_attn_shape* shape, hipStream_t stream) {
     int rc;
     if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
         (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)))
@@ -1626,7 +1637,7 @@ int attn_fwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
     FwdArgs a;
     a.q = tns(q); a.k = tns(k); a.v = tns(v);
     a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o->sb; a.o_sh = o->sh; a.o_ss = o->ss;
-    a.lse = lse;
+    a.lse = lse; a.lse_ld = (int)lse_ld;
     a.kmask = key_mask; a.kmask_ld = key_mask_ld;
     a.B = shape->B; a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.S = shape->S;
     a.sl2 = shape->scale * 1.4426950408889634f;
@@ -1645,7 +1656,7 @@ int attn_fwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
 }
 
 int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
-             const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
+             const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws, int64_t lse_ld,
              const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
              const uint64_t* key_mask, int64_t key_mask_ld, DropArgs drop, DocArgs docs, const smt_attn_shape* shape,
              hipStream_t stream) {
@@ -1655,7 +1666,9 @@ int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
         (rc = check_tensor(dq, "dq", fn)) || (rc = check_tensor(dk, "dk", fn)) || (rc = check_tensor(dv, "dv", fn)))
         return rc;
     if (!lse || !delta_ws) return fail(-1, "%s: null lse / delta workspace", fn);
-    if (!al16(lse) || !al16(delta_ws) || (shape->S & 3)) return fail(-2, "%s: lse / delta need 16-byte rows (S %% 4 == 0)", fn);
+    // lse_ld == S from the entry points without a stride of their own (the *_ld ones refuse such a stride first)
+    if (lse_ld & 3) return fail(-2, "%s: lse / delta need 16-byte rows (S %% 4 == 0; any S through smt_attn_bwd_ld)", fn);
+    if (!al16(lse) || !al16(delta_ws)) return fail(-2, "%s: lse / delta need 16-byte aligned base pointers", fn);
     if (key_mask && key_mask_ld < (shape->S + 63) / 64)
         return fail(-1, "%s: key_mask_ld %lld < ceil(S / 64)", fn, (long long)key_mask_ld);
     const int B = shape->B, Hq = shape->Hq, Hkv = shape->Hkv, S = shape->S;
@@ -1665,7 +1678,7 @@ int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
     DqArgs qa;
     qa.q = tns(q); qa.k = tns(k); qa.v = tns(v); qa.dout = tns(d_o); qa.o = tns(o);
     qa.dq = static_cast<uint16_t*>(dq->ptr); qa.dq_sb = dq->sb; qa.dq_sh = dq->sh; qa.dq_ss = dq->ss;
-    qa.lse = lse; qa.delta = delta_ws;
+    qa.lse = lse; qa.delta = delta_ws; qa.lse_ld = (int)lse_ld;
     qa.kmask = key_mask; qa.kmask_ld = key_mask_ld;
     qa.B = B; qa.Hq = Hq; qa.Hkv = Hkv; qa.S = S; qa.sl2 = sl2; qa.scale = shape->scale;
     qa.drop = drop;
@@ -1680,7 +1693,7 @@ int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
     ka.q = tns(q); ka.k = tns(k); ka.v = tns(v); ka.dout = tns(d_o);
     ka.dk = static_cast<uint16_t*>(dk->ptr); ka.dk_sb = dk->sb; ka.dk_sh = dk->sh; ka.dk_ss = dk->ss;
     ka.dv = static_cast<uint16_t*>(dv->ptr); ka.dv_sb = dv->sb; ka.dv_sh = dv->sh; ka.dv_ss = dv->ss;
-    ka.lse = lse; ka.delta = delta_ws;
+    ka.lse = lse; ka.delta = delta_ws; ka.lse_ld = (int)lse_ld;
     ka.kmask = key_mask; ka.kmask_ld = key_mask_ld;
     ka.B = B; ka.Hq = Hq; ka.Hkv = Hkv; ka.S = S; ka.sl2 = sl2; ka.scale = shape->scale;
     ka.drop = drop;
@@ -1693,6 +1706,18 @@ int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
 }
 
 constexpr DropArgs kNoDrop = {nullptr, 0u, 1.f};
+
+// what only the *_ld entry points can get wrong: the stride, and documents beside a key mask (the
+// shape itself is checked by attn_fwd / attn_bwd, a null one included)
+int check_ld(const char* fn, int64_t lse_ld, const uint64_t* key_mask, const int32_t* doc_start, const int32_t* doc_end,
+             const smt_attn_shape* shape) {
+    if (shape && lse_ld < shape->S) return fail(-1, "%s: lse_ld %lld < S %d", fn, (long long)lse_ld, shape->S);
+    if (lse_ld & 3) return fail(-1, "%s: lse_ld %lld is not a multiple of 4 (16-byte rows)", fn, (long long)lse_ld);
+    if (lse_ld > 0x7fffffffLL) return fail(-1, "%s: lse_ld %lld is above 2^31 - 1", fn, (long long)lse_ld);
+    if (!doc_start != !doc_end) return fail(-1, "%s: doc_start and doc_end come together (one is null)", fn);
+    if (doc_start && key_mask) return fail(-1, "%s: a key mask and documents together are not supported", fn);
+    return 0;
+}
 
 // Cached forward: column blocks of a call, and the default split count. Host arithmetic only.
 int dec_col_blocks(const smt_attn_shape* s, int32_t Sq) {
@@ -1737,8 +1762,8 @@ const char* smt_attn_last_error(void) { return g_err; }
 int smt_attn_fwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
                        const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
                        const smt_attn_shape* shape, hipStream_t stream) {
-    return attn_fwd(key_mask ? "smt_attn_fwd_kmask" : "smt_attn_fwd", q, k, v, o, lse, key_mask, key_mask_ld, kNoDrop,
-                    kNoDocs, shape, stream);
+    return attn_fwd(key_mask ? "smt_attn_fwd_kmask" : "smt_attn_fwd", q, k, v, o, lse, shape ? shape->S : 0, key_mask,
+                    key_mask_ld, kNoDrop, kNoDocs, shape, stream);
 }
 
 int smt_attn_fwd(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1751,8 +1776,8 @@ int smt_attn_bwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const
                        const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
                        const uint64_t* key_mask, int64_t key_mask_ld, const smt_attn_shape* shape,
                        hipStream_t stream) {
-    return attn_bwd(key_mask ? "smt_attn_bwd_kmask" : "smt_attn_bwd", q, k, v, o, d_o, lse, delta_ws, dq, dk, dv,
-                    key_mask, key_mask_ld, kNoDrop, kNoDocs, shape, stream);
+    return attn_bwd(key_mask ? "smt_attn_bwd_kmask" : "smt_attn_bwd", q, k, v, o, d_o, lse, delta_ws,
+                    shape ? shape->S : 0, dq, dk, dv, key_mask, key_mask_ld, kNoDrop, kNoDocs, shape, stream);
 }
 
 int smt_attn_bwd(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1771,7 +1796,8 @@ int smt_attn_fwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, con
     int rc;
     if ((rc = check_drop(p, seed, "smt_attn_fwd_dropout", &drop))) return rc;
     if (drop.t == 0) return smt_attn_fwd_kmask(q, k, v, o, lse, key_mask, key_mask_ld, shape, stream);
-    return attn_fwd("smt_attn_fwd_dropout", q, k, v, o, lse, key_mask, key_mask_ld, drop, kNoDocs, shape, stream);
+    return attn_fwd("smt_attn_fwd_dropout", q, k, v, o, lse, shape ? shape->S : 0, key_mask, key_mask_ld, drop, kNoDocs,
+                    shape, stream);
 }
 
 int smt_attn_bwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1784,8 +1810,8 @@ int smt_attn_bwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, con
     if ((rc = check_drop(p, seed, "smt_attn_bwd_dropout", &drop))) return rc;
     if (drop.t == 0)
         return smt_attn_bwd_kmask(q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, key_mask, key_mask_ld, shape, stream);
-    return attn_bwd("smt_attn_bwd_dropout", q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, key_mask, key_mask_ld, drop, kNoDocs,
-                    shape, stream);
+    return attn_bwd("smt_attn_bwd_dropout", q, k, v, o, d_o, lse, delta_ws, shape ? shape->S : 0, dq, dk, dv, key_mask,
+                    key_mask_ld, drop, kNoDocs, shape, stream);
 }
 
 int smt_attn_fwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1797,7 +1823,7 @@ int smt_attn_fwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const 
     DropArgs drop;
     int rc;
     if ((rc = check_drop(p, seed, fn, &drop))) return rc;
-    return attn_fwd(fn, q, k, v, o, lse, nullptr, 0, drop, DocArgs{doc_start, doc_end}, shape, stream);
+    return attn_fwd(fn, q, k, v, o, lse, shape ? shape->S : 0, nullptr, 0, drop, DocArgs{doc_start, doc_end}, shape, stream);
 }
 
 int smt_attn_bwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1812,8 +1838,32 @@ int smt_attn_bwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const 
     DropArgs drop;
     int rc;
     if ((rc = check_drop(p, seed, fn, &drop))) return rc;
-    return attn_bwd(fn, q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, nullptr, 0, drop, DocArgs{doc_start, doc_end}, shape,
-                    stream);
+    return attn_bwd(fn, q, k, v, o, d_o, lse, delta_ws, shape ? shape->S : 0, dq, dk, dv, nullptr, 0, drop,
+                    DocArgs{doc_start, doc_end}, shape, stream);
+}
+
+int smt_attn_fwd_ld(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                    const smt_attn_tensor* o, float* lse, int64_t lse_ld, const uint64_t* key_mask, int64_t key_mask_ld,
+                    const int32_t* doc_start, const int32_t* doc_end, float p, const uint64_t* seed,
+                    const smt_attn_shape* shape, hipStream_t stream) {
+    const char* fn = "smt_attn_fwd_ld";
+    DropArgs drop;
+    int rc;
+    if ((rc = check_ld(fn, lse_ld, key_mask, doc_start, doc_end, shape)) || (rc = check_drop(p, seed, fn, &drop))) return rc;
+    return attn_fwd(fn, q, k, v, o, lse, lse_ld, key_mask, key_mask_ld, drop, DocArgs{doc_start, doc_end}, shape, stream);
+}
+
+int smt_attn_bwd_ld(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                    const smt_attn_tensor* o, const smt_attn_tensor* d_o, const float* lse, float* delta_ws,
+                    int64_t lse_ld, const smt_attn_tensor* dq, const smt_attn_tensor* dk, const smt_attn_tensor* dv,
+                    const uint64_t* key_mask, int64_t key_mask_ld, const int32_t* doc_start, const int32_t* doc_end,
+                    float p, const uint64_t* seed, const smt_attn_shape* shape, hipStream_t stream) {
+    const char* fn = "smt_attn_bwd_ld";
+    DropArgs drop;
+    int rc;
+    if ((rc = check_ld(fn, lse_ld, key_mask, doc_start, doc_end, shape)) || (rc = check_drop(p, seed, fn, &drop))) return rc;
+    return attn_bwd(fn, q, k, v, o, d_o, lse, delta_ws, lse_ld, dq, dk, dv, key_mask, key_mask_ld, drop,
+                    DocArgs{doc_start, doc_end}, shape, stream);
 }
 
 int smt_attn_dropout_mask(uint8_t* keep, float p, const uint64_t* seed, const smt_attn_shape* shape,

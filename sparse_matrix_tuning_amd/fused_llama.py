@@ -899,25 +899,29 @@ class FlashAttnFn(torch.autograd.Function):
     (packed rows; not together with a key mask). ``dropout_p``: attention dropout inside
     the kernels (the keep function of include/smt_attention.h; effective rate
     :func:`dropout_effective_p`); ``seed``: an int or a 1-element int64 device tensor, drawn from the
-    device generator when None (no host sync; ``torch.utils.checkpoint`` replays it)."""
+    device generator when None (no host sync; ``torch.utils.checkpoint`` replays it). ``any_length``:
+    take any S >= 1 (default: S % 4 == 0 only, as before the ``smt_attn_*_ld`` entry points). Either
+    way lse and delta are ``[B, Hq, lse_ld]`` with ``lse_ld = (S + 3) & ~3``, the 16-byte rows the
+    dK / dV kernel fetches; q, k, v, o and do are never padded or copied for the length."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, key_mask=None, joint=False, dropout_p=0.0, seed=None, doc_mask=None):
+    def forward(ctx, q, k, v, scale, key_mask=None, joint=False, dropout_p=0.0, seed=None, doc_mask=None,
+                any_length=False):
         if doc_mask is not None and key_mask is not None:
             raise NotImplementedError(_DOC_AND_KEY_MASK)
         for t, n in ((q, "q"), (k, "k"), (v, "v")):
             _need(t, "flash attention " + n, like=q)
         B, Hq, S, D = q.shape
         Hkv = k.shape[1]
-        if D != 128 or k.shape != (B, Hkv, S, D) or v.shape != k.shape or Hq % Hkv or S % 4:
+        if D != 128 or k.shape != (B, Hkv, S, D) or v.shape != k.shape or Hq % Hkv or S < 1 or (S % 4 and not any_length):
             raise NotImplementedError(f"flash attention: head_dim 128, Hq % Hkv == 0, S % 4 == 0 "
-                                      f"(q {tuple(q.shape)}, k {tuple(k.shape)})")
+                                      f"(any S >= 1 with any_length=True) (q {tuple(q.shape)}, k {tuple(k.shape)})")
         q, k, v = _attn_ready(q), _attn_ready(k), _attn_ready(v)
         for t in (q, k, v):
             if S * t.stride(2) * 2 >= 2 ** 31:
                 raise NotImplementedError("flash attention: per-head extent must stay below 2 GiB")
         o = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
-        lse = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+        lse = torch.empty(B, Hq, (S + 3) & ~3, dtype=torch.float32, device=q.device)
         ov = o.transpose(1, 2)
         shape = _hip.AttnShape(B, Hq, Hkv, S, float(scale), _dt(q))
         km, km_ld = None, 0
@@ -938,25 +942,15 @@ class FlashAttnFn(torch.autograd.Function):
         if dropout_p != 0.0 and dropout_threshold(dropout_p):
             seed_t = (torch.empty(1, dtype=torch.int64, device=q.device).random_() if seed is None
                       else _seed_tensor(seed, q.device))
-        if doc_mask is not None:
-            rc = _hip.load().smt_attn_fwd_docs(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
-                                               ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
-                                               lse.data_ptr(), ds.data_ptr(), de.data_ptr(),
-                                               dropout_p if seed_t is not None else 0.0,
-                                               seed_t.data_ptr() if seed_t is not None else None,
-                                               ctypes.byref(shape), _stream(q))
-            _hip._check(rc, "smt_attn_fwd_docs")
-        elif seed_t is not None:
-            rc = _hip.load().smt_attn_fwd_dropout(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
-                                                  ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
-                                                  lse.data_ptr(), km, km_ld, dropout_p, seed_t.data_ptr(),
-                                                  ctypes.byref(shape), _stream(q))
-            _hip._check(rc, "smt_attn_fwd_dropout")
-        else:
-            rc = _hip.load().smt_attn_fwd_kmask(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
-                                                ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
-                                                lse.data_ptr(), km, km_ld, ctypes.byref(shape), _stream(q))
-            _hip._check(rc, "smt_attn_fwd")
+        rc = _hip.load().smt_attn_fwd_ld(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
+                                         ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
+                                         lse.data_ptr(), lse.shape[2], km, km_ld,
+                                         ds.data_ptr() if ds is not None else None,
+                                         de.data_ptr() if de is not None else None,
+                                         dropout_p if seed_t is not None else 0.0,
+                                         seed_t.data_ptr() if seed_t is not None else None,
+                                         ctypes.byref(shape), _stream(q))
+        _hip._check(rc, "smt_attn_fwd_ld")
         ctx.save_for_backward(q, k, v, o, lse, key_mask.bits if key_mask is not None else None, seed_t, ds, de)
         ctx.dropout_p = dropout_p
         ctx.scale = float(scale)
@@ -982,43 +976,28 @@ class FlashAttnFn(torch.autograd.Function):
             dq = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device)
             dk = torch.empty_strided(k.shape, k.stride(), dtype=k.dtype, device=k.device)
             dv = torch.empty_strided(v.shape, v.stride(), dtype=v.dtype, device=v.device)
-        delta = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+        delta = torch.empty_like(lse)
         if do.dtype != q.dtype:
             do = do.to(q.dtype)
         shape = _hip.AttnShape(B, Hq, Hkv, S, ctx.scale, _dt(q))
         T = _attn_tensor
-        if ds is not None:
-            rc = _hip.load().smt_attn_bwd_docs(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
-                                               ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
-                                               lse.data_ptr(), delta.data_ptr(), ctypes.byref(T(dq)),
-                                               ctypes.byref(T(dk)), ctypes.byref(T(dv)), ds.data_ptr(), de.data_ptr(),
-                                               ctx.dropout_p if seed_t is not None else 0.0,
-                                               seed_t.data_ptr() if seed_t is not None else None,
-                                               ctypes.byref(shape), _stream(q))
-            _hip._check(rc, "smt_attn_bwd_docs")
-            return dq, dk, dv, None, None, None, None, None, None
-        if seed_t is not None:
-            rc = _hip.load().smt_attn_bwd_dropout(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
-                                                  ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
-                                                  lse.data_ptr(), delta.data_ptr(), ctypes.byref(T(dq)),
-                                                  ctypes.byref(T(dk)), ctypes.byref(T(dv)),
-                                                  km.data_ptr() if km is not None else None,
-                                                  km.shape[1] if km is not None else 0, ctx.dropout_p,
-                                                  seed_t.data_ptr(), ctypes.byref(shape), _stream(q))
-            _hip._check(rc, "smt_attn_bwd_dropout")
-            return dq, dk, dv, None, None, None, None, None, None
-        rc = _hip.load().smt_attn_bwd_kmask(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
-                                            ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
-                                            lse.data_ptr(), delta.data_ptr(), ctypes.byref(T(dq)),
-                                            ctypes.byref(T(dk)), ctypes.byref(T(dv)),
-                                            km.data_ptr() if km is not None else None,
-                                            km.shape[1] if km is not None else 0, ctypes.byref(shape), _stream(q))
-        _hip._check(rc, "smt_attn_bwd")
-        return dq, dk, dv, None, None, None, None, None, None
+        rc = _hip.load().smt_attn_bwd_ld(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
+                                         ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
+                                         lse.data_ptr(), delta.data_ptr(), lse.shape[2], ctypes.byref(T(dq)),
+                                         ctypes.byref(T(dk)), ctypes.byref(T(dv)),
+                                         km.data_ptr() if km is not None else None,
+                                         km.shape[1] if km is not None else 0,
+                                         ds.data_ptr() if ds is not None else None,
+                                         de.data_ptr() if de is not None else None,
+                                         ctx.dropout_p if seed_t is not None else 0.0,
+                                         seed_t.data_ptr() if seed_t is not None else None,
+                                         ctypes.byref(shape), _stream(q))
+        _hip._check(rc, "smt_attn_bwd_ld")
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 def flash_attention(q, k, v, scale=None, key_mask: "KeyMask" = None, joint: bool = False, dropout_p: float = 0.0,
-                    seed=None, doc_mask: "DocMask" = None):
+                    seed=None, doc_mask: "DocMask" = None, any_length: bool = False):
     """Causal attention ``[B, Hq, S, 128]`` x ``[B, Hkv, S, 128]`` -> ``[B, S, Hq, 128]``; with
     ``key_mask`` the keys it clears take no part (padded batches). ``joint``: the gradients of q, k
     and v go out as slices of one ``[B, S, (Hq + 2 Hkv) * 128]`` buffer (same values). ``dropout_p``:
@@ -1026,11 +1005,13 @@ def flash_attention(q, k, v, scale=None, key_mask: "KeyMask" = None, joint: bool
     :func:`dropout_effective_p`, mask :func:`flash_dropout_mask`); ``seed``: an int or a 1-element
     int64 device tensor, drawn from the device generator when None. ``doc_mask``: a :class:`DocMask`
     for packed rows (block-diagonal causal attention; the kernels skip the K/V tiles no row of a
-    workgroup sees); not together with ``key_mask``."""
+    workgroup sees); not together with ``key_mask``. ``any_length``: take any ``S >= 1``, forward and
+    backward, natively (no padded copies); the default refuses ``S % 4 != 0`` as it always did. At
+    ``S % 4 == 0`` both give the same bits."""
     if doc_mask is not None and key_mask is not None:
         raise NotImplementedError(_DOC_AND_KEY_MASK)
     return FlashAttnFn.apply(q, k, v, scale if scale is not None else q.shape[-1] ** -0.5, key_mask, joint,
-                             dropout_p, seed, doc_mask)
+                             dropout_p, seed, doc_mask, any_length)
 
 
 class CacheMask:
@@ -1115,9 +1096,12 @@ def smt_flash_attention_forward(module, query, key, value, attention_mask, dropo
 
     A call against a KV cache (a :class:`CacheMask` from :func:`smt_flash_mask`, or fewer queries than
     keys) runs :func:`flash_attention_cached`, forward only: dropout or a :class:`DocMask` with a
-    cache raises. So does a same-length call whose length is not a multiple of 4 when it needs no
-    gradient (the prefill of an odd-length prompt; the training kernels need ``S % 4 == 0``). Every
-    other same-length call goes to :func:`flash_attention` as before."""
+    cache raises. Every same-length call goes to :func:`flash_attention` with ``any_length=True``: the
+    reference's collator pads a batch to its longest sample (helper.py:191-205), so S is any integer in
+    training, in the evaluation loss and in the prefill of ``generate()``. A gradient-free call takes
+    that route too: at B 16, Hq 32, Hkv 8 the training forward measured 3.3-3.7x (S 2047) and 2.1x
+    (S 301) faster than the cached kernel, which re-reads K / V once per 32 / G query positions
+    ("Any sequence length"; profiles/r10_anylen_forward_routes.jsonl)."""
     if attention_mask is not None and not isinstance(attention_mask, (KeyMask, DocMask, CacheMask)):
         raise NotImplementedError("smt_flash attention: only key-padding and document masks built by smt_flash_mask "
                                   f"are supported (got {type(attention_mask).__name__})")
@@ -1138,14 +1122,11 @@ def smt_flash_attention_forward(module, query, key, value, attention_mask, dropo
                                  f"cache holds {Skv}")
             km, q_offset = attention_mask.key_mask, attention_mask.q_offset
         return flash_attention_cached(query, key, value, scaling, km, q_offset), None
-    if (Sq % 4 and dropout == 0.0 and not isinstance(attention_mask, DocMask)
-            and not (torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad))):
-        return flash_attention_cached(query, key, value, scaling, attention_mask, 0), None
     # the engine marks attention modules whose q/k/v_proj share a joint transposed copy
     docs = attention_mask if isinstance(attention_mask, DocMask) else None
     return flash_attention(query, key, value, scaling, None if docs is not None else attention_mask,
                            joint=getattr(module, "_smt_joint_qkv_grad", False), dropout_p=dropout,
-                           doc_mask=docs), None
+                           doc_mask=docs, any_length=True), None
 
 
 def _closure_vars(fn) -> dict:
