@@ -212,6 +212,36 @@ int     smt_attn_fwd_cached(const smt_attn_tensor* q, const smt_attn_tensor* k, 
                             int32_t Sq, int32_t q_offset, int32_t num_splits, void* workspace,
                             const smt_attn_shape* shape, hipStream_t stream);
 
+/*
+ * The same call with the position on the device (additive; the ABI version is unchanged): for a
+ * pre-allocated ("static") cache whose fill level the host does not know, and for capturing the call
+ * in a HIP graph: no launch parameter depends on the position.
+ *   positions         int64 device memory, 8-byte aligned; row b's first query sits at
+ *                     p = positions[b * positions_stride], read by the kernel (never by the host)
+ *   positions_stride  0: one position for the whole batch; 1: one per batch row
+ *   shape->S = Skv    the CAPACITY of the K / V buffers; key_mask covers the capacity
+ * Query i of row b sees key j iff j <= p + i and key j's mask bit is set; the keys any query of the row
+ * sees are [0, p + Sq), and K / V rows at p + Sq and later are never read, whatever they hold. The
+ * kernel derives from p what smt_attn_fwd_cached derives from q_offset on the host, the tile partition
+ * included (tiles = ceil((p + Sq) / 64), ceil(tiles / num_splits) per split, per batch row): for a
+ * given num_splits the result is bit-identical to smt_attn_fwd_cached with q_offset = p on the same
+ * tensors. The grid, num_splits == 0 (smt_attn_cached_splits) and the workspace
+ * (smt_attn_cached_workspace) are sized from the capacity; a split that ends up without tiles
+ * contributes nothing, so a cache far from full runs more, emptier splits than the host-offset call.
+ *
+ * A position the host would have refused cannot be refused here: the kernel SATURATES p into
+ * [0, Skv - Sq] before it forms any address, and computes the result of that position. No read or
+ * write outside the tensors depends on the values in `positions`.
+ *
+ * Returns before any HIP call: -1 for what smt_attn_fwd_cached refuses (q_offset apart), null
+ * positions, positions_stride other than 0 or 1, Sq > Skv; -2 for positions that are not 8-byte aligned
+ * and when Skv rows of K or V span 2 GiB or more.
+ */
+int     smt_attn_fwd_cached_pos(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                                const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
+                                int32_t Sq, const int64_t* positions, int32_t positions_stride, int32_t num_splits,
+                                void* workspace, const smt_attn_shape* shape, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

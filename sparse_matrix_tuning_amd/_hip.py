@@ -45,6 +45,7 @@ ABI_FUNCTIONS = (
     "smt_attn_dropout_threshold", "smt_attn_fwd_dropout", "smt_attn_bwd_dropout", "smt_attn_dropout_mask",
     "smt_attn_fwd_docs", "smt_attn_bwd_docs", "smt_attn_fwd_ld", "smt_attn_bwd_ld",
     "smt_attn_cached_splits", "smt_attn_cached_workspace", "smt_attn_fwd_cached",
+    "smt_attn_fwd_cached_pos",
     "smt_fp8_last_error", "smt_quant_rows_e4m3", "smt_quant_cols_t_e4m3", "smt_quant_rows_cat_e4m3",
     "smt_swiglu_fwd_quant_e4m3", "smt_swiglu_bwd_quant_e4m3", "smt_swiglu_bwd_quant_e4m3_packed",
     "smt_rmsnorm_fwd_quant_e4m3",
@@ -180,6 +181,8 @@ _SIGS = {
     "smt_attn_cached_workspace": (_I64, [ctypes.POINTER(AttnShape), _I32, _I32]),
     "smt_attn_fwd_cached": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 4 + [_P, _P, _I64, _I32, _I32, _I32, _P,
                                            ctypes.POINTER(AttnShape), _P]),
+    "smt_attn_fwd_cached_pos": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 4 + [_P, _P, _I64, _I32, _P, _I32, _I32, _P,
+                                               ctypes.POINTER(AttnShape), _P]),
     "smt_model_ops_last_error": (ctypes.c_char_p, []),
     "smt_rmsnorm_fwd": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _I32, ctypes.c_float, _I32, _P]),
     "smt_rmsnorm_bwd_waves": (ctypes.c_int, [_I64]),

@@ -2,7 +2,8 @@
 // dtype, smt_attn_shape.dtype; ABI v13), fp32 softmax, optional attention dropout inside the three
 // kernels (DROP instances, smt_attn_*_dropout), optional document mask of packed rows (DOC instances,
 // smt_attn_*_docs); and the forward-only split-KV kernel of calls against a KV cache (attn_decode_kernel,
-// smt_attn_fwd_cached). Any sequence length S >= 1, forward and backward: lse and delta are
+// smt_attn_fwd_cached; smt_attn_fwd_cached_pos with the query position read on the device, for a
+// pre-allocated cache). Any sequence length S >= 1, forward and backward: lse and delta are
 // [B][Hq][lse_ld] with a row stride lse_ld % 4 == 0 of their own (smt_attn_fwd_ld / smt_attn_bwd_ld),
 // which is all the 16-byte lse / delta fetch of the dK/dV kernel needs; the other entry points are
 // these with lse_ld = S.
@@ -28,6 +29,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "smt_attention.h"
@@ -1359,6 +1361,10 @@ struct DecArgs {
     int Hq, Hkv, G, Sq, q_offset, ncols, ncb, nsplit, tps;     // ncols = Sq * G; tps = tiles per split
     float sl2;
 };
+struct DecPosArgs : DecArgs {              // the device-position form (DecArgs itself keeps its size)
+    const int64_t* pos;
+    int pos_stride, cap;
+};
 
 __device__ __forceinline__ float* dec_ws_o(const DecArgs& a, int64_t slot, int col) {
     return a.ws + (slot * kDecCols + col) * kD;
@@ -1367,21 +1373,36 @@ __device__ __forceinline__ float* dec_ws_ml(const DecArgs& a, int64_t nslots, in
     return a.ws + nslots * kDecCols * kD + (slot * kDecCols + col) * 2;
 }
 
-template <bool KMASK, int F, bool DIRECT>
+// Args = DecPosArgs (smt_attn_fwd_cached_pos): the position of row b's first query is
+// a.pos[b * a.pos_stride], read here and saturated into [0, cap - Sq] (cap = the K / V buffers' row count; Sq <= cap is checked by
+// the host) before anything is derived from it, so no address depends on an out-of-contract value.
+// The tile partition is then the one the host computes for that q_offset, and the grid is sized from
+// the capacity. With Args = DecArgs, a.q_offset and a.tps are taken as they are.
+template <bool KMASK, int F, bool DIRECT, class Args>
 __global__ __launch_bounds__(64)
-void attn_decode_kernel(DecArgs a) {
+void attn_decode_kernel(Args a) {
+    constexpr bool POS = std::is_same<Args, DecPosArgs>::value;
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // K/V ring: 2 x 32 KiB
     const int cb = blockIdx.x, sp = blockIdx.y, bh = blockIdx.z;
     const int b = bh / a.Hkv, hk = bh - b * a.Hkv;
+    int q_offset = a.q_offset, tps = a.tps;
+    if constexpr (POS) {
+        int64_t p = a.pos[(int64_t)b * a.pos_stride];          // workgroup-uniform
+        const int64_t p_max = (int64_t)a.cap - a.Sq;
+        p = p < 0 ? 0 : (p > p_max ? p_max : p);
+        q_offset = __builtin_amdgcn_readfirstlane((int)p);
+        const int tiles = (q_offset + a.Sq + kKV - 1) / kKV;
+        tps = (tiles + a.nsplit - 1) / a.nsplit;
+    }
     const int lane = threadIdx.x, hi = lane >> 5, l32 = lane & 31;
     const int col = cb * kDecCols + l32;
     const bool cvalid = col < a.ncols;
     const int qi = cvalid ? col / a.G : 0;
     const int h = hk * a.G + (cvalid ? col - qi * a.G : 0);
-    const int qpos = cvalid ? a.q_offset + qi : -1;            // an unused column sees no key
-    // keys this column block can see: [0, kv_end), kv_end <= Skv (checked by the host)
-    const int kv_end = a.q_offset + min(a.Sq - 1, (cb * kDecCols + kDecCols - 1) / a.G) + 1;
-    const int t0 = sp * a.tps, t1 = min((kv_end + kKV - 1) / kKV, t0 + a.tps);
+    const int qpos = cvalid ? q_offset + qi : -1;            // an unused column sees no key
+    // keys this column block can see: [0, kv_end), kv_end <= Skv (checked by the host, or by the clamp)
+    const int kv_end = q_offset + min(a.Sq - 1, (cb * kDecCols + kDecCols - 1) / a.G) + 1;
+    const int t0 = sp * tps, t1 = min((kv_end + kKV - 1) / kKV, t0 + tps);
     const int64_t nslots = (int64_t)gridDim.z * a.ncb * a.nsplit;
     const int64_t slot = ((int64_t)bh * a.ncb + cb) * a.nsplit + sp;
     if (t0 >= t1) {                                            // an empty split (never with DIRECT)
@@ -1741,16 +1762,87 @@ int64_t dec_workspace(const smt_attn_shape* s, int32_t Sq, int32_t num_splits) {
     return (int64_t)s->B * s->Hkv * dec_col_blocks(s, Sq) * num_splits * kDecPartial * (int64_t)sizeof(float);
 }
 
-#define SMT_ATTN_LAUNCH_DEC(F, kmask, direct, grid, stream, args)                                                \
+#define SMT_ATTN_LAUNCH_DEC(F, kmask, direct, Args, grid, stream, args)                                          \
     do {                                                                                                      \
         if (kmask) {                                                                                          \
-            if (direct) hipLaunchKernelGGL((attn_decode_kernel<true, F, true>), grid, dim3(64), 0, stream, args);  \
-            else hipLaunchKernelGGL((attn_decode_kernel<true, F, false>), grid, dim3(64), 0, stream, args);   \
+            if (direct) hipLaunchKernelGGL((attn_decode_kernel<true, F, true, Args>), grid, dim3(64), 0, stream, args);  \
+            else hipLaunchKernelGGL((attn_decode_kernel<true, F, false, Args>), grid, dim3(64), 0, stream, args);   \
         } else {                                                                                              \
-            if (direct) hipLaunchKernelGGL((attn_decode_kernel<false, F, true>), grid, dim3(64), 0, stream, args); \
-            else hipLaunchKernelGGL((attn_decode_kernel<false, F, false>), grid, dim3(64), 0, stream, args);  \
+            if (direct) hipLaunchKernelGGL((attn_decode_kernel<false, F, true, Args>), grid, dim3(64), 0, stream, args); \
+            else hipLaunchKernelGGL((attn_decode_kernel<false, F, false, Args>), grid, dim3(64), 0, stream, args);  \
         }                                                                                                     \
     } while (0)
+
+// smt_attn_fwd_cached (pos == nullptr: the position is q_offset) and smt_attn_fwd_cached_pos (the
+// position is read by the kernel; q_offset is unused and the bounds are taken on the capacity Skv).
+int attn_fwd_cached(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                    const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld, int32_t Sq,
+                    int32_t q_offset, const int64_t* pos, int32_t pos_stride, bool by_pos, int32_t num_splits,
+                    void* workspace, const smt_attn_shape* shape, hipStream_t stream) {
+    int rc;
+    if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
+        (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)))
+        return rc;
+    const int Skv = shape->S;
+    if (Sq < 1) return fail(-1, "%s: Sq = %d (at least one query position)", fn, (int)Sq);
+    if (by_pos) {
+        if (!pos) return fail(-1, "%s: null positions", fn);
+        if (reinterpret_cast<uintptr_t>(pos) & 7u) return fail(-2, "%s: positions need 8-byte alignment (int64)", fn);
+        if (pos_stride != 0 && pos_stride != 1)
+            return fail(-1, "%s: positions_stride = %d (0: one position for the batch, 1: one per row)", fn, (int)pos_stride);
+        if (Sq > Skv) return fail(-1, "%s: Sq %d > Skv %d (a query without a key slot of its own)", fn, (int)Sq, Skv);
+    } else {
+        if (q_offset < 0) return fail(-1, "%s: q_offset = %d is negative", fn, (int)q_offset);
+        if ((int64_t)q_offset + Sq > Skv)
+            return fail(-1, "%s: q_offset %d + Sq %d > Skv %d (a query without a key slot of its own)", fn, (int)q_offset,
+                        (int)Sq, Skv);
+    }
+    if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
+    if (key_mask && key_mask_ld < (Skv + 63) / 64)
+        return fail(-1, "%s: key_mask_ld %lld < ceil(Skv / 64)", fn, (long long)key_mask_ld);
+    const int nsplit = num_splits ? num_splits : dec_default_splits(shape, Sq);
+    if (nsplit > 65535) return fail(-1, "%s: num_splits = %d is above 65535", fn, nsplit);
+    if (nsplit > 1 && !workspace)
+        return fail(-1, "%s: null workspace with %d splits (smt_attn_cached_workspace bytes)", fn, nsplit);
+    if (nsplit > 1 && !al16(workspace)) return fail(-2, "%s: workspace needs 16-byte alignment", fn);
+    // keys any query of the call sees: [0, kv_all); a device position can reach the whole capacity
+    const int kv_all = by_pos ? Skv : q_offset + Sq;
+    if ((int64_t)kv_all * k->ss * 2 >= 0x7fffffffLL || (int64_t)kv_all * v->ss * 2 >= 0x7fffffffLL)
+        return fail(-2, "%s: the visible K / V rows of one head must span less than 2 GiB", fn);
+    const int64_t ncols = (int64_t)Sq * (shape->Hq / shape->Hkv);
+    const int64_t bh = (int64_t)shape->B * shape->Hkv;
+    if (ncols > 0x7fffffffLL / 2 || bh > 65535) return fail(-1, "%s: B * Hkv must stay within 65535 and Sq * G below 2^30", fn);
+    DecArgs a;
+    a.q = tns(q); a.k = tns(k); a.v = tns(v);
+    a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o->sb; a.o_sh = o->sh; a.o_ss = o->ss;
+    a.lse = lse;
+    a.kmask = key_mask; a.kmask_ld = key_mask_ld;
+    a.ws = static_cast<float*>(workspace);
+    a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.G = shape->Hq / shape->Hkv;
+    a.Sq = Sq; a.q_offset = by_pos ? 0 : q_offset;
+    a.ncols = (int)ncols; a.ncb = dec_col_blocks(shape, Sq); a.nsplit = nsplit;
+    const int tiles = (kv_all + kKV - 1) / kKV;
+    a.tps = (tiles + nsplit - 1) / nsplit;                 // by_pos: the kernel's own, from its position
+    a.sl2 = shape->scale * 1.4426950408889634f;
+    const dim3 grid((unsigned)a.ncb, (unsigned)nsplit, (unsigned)bh);
+    if (by_pos) {
+        DecPosArgs ap;
+        static_cast<DecArgs&>(ap) = a;
+        ap.pos = pos; ap.pos_stride = pos_stride; ap.cap = Skv;
+        if (shape->dtype == SMT_DTYPE_FP16) SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_FP16, key_mask, nsplit == 1, DecPosArgs, grid, stream, ap);
+        else SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_BF16, key_mask, nsplit == 1, DecPosArgs, grid, stream, ap);
+    } else if (shape->dtype == SMT_DTYPE_FP16) {
+        SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_FP16, key_mask, nsplit == 1, DecArgs, grid, stream, a);
+    } else {
+        SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_BF16, key_mask, nsplit == 1, DecArgs, grid, stream, a);
+    }
+    if ((rc = check_launch("attn_decode_kernel")) || nsplit == 1) return rc;
+    const dim3 cgrid((unsigned)ncols, (unsigned)bh);
+    if (shape->dtype == SMT_DTYPE_FP16)
+        hipLaunchKernelGGL(attn_decode_combine_kernel<SMT_DTYPE_FP16>, cgrid, dim3(kD), 0, stream, a);
+    else hipLaunchKernelGGL(attn_decode_combine_kernel<SMT_DTYPE_BF16>, cgrid, dim3(kD), 0, stream, a);
+    return check_launch("attn_decode_combine_kernel");
+}
 
 }  // namespace
 
@@ -1907,52 +1999,16 @@ int smt_attn_fwd_cached(const smt_attn_tensor* q, const smt_attn_tensor* k, cons
                         const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
                         int32_t Sq, int32_t q_offset, int32_t num_splits, void* workspace,
                         const smt_attn_shape* shape, hipStream_t stream) {
-    const char* fn = "smt_attn_fwd_cached";
-    int rc;
-    if ((rc = check_shape(shape, fn)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(k, "k", fn)) ||
-        (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)))
-        return rc;
-    const int Skv = shape->S;
-    if (Sq < 1) return fail(-1, "%s: Sq = %d (at least one query position)", fn, (int)Sq);
-    if (q_offset < 0) return fail(-1, "%s: q_offset = %d is negative", fn, (int)q_offset);
-    if ((int64_t)q_offset + Sq > Skv)
-        return fail(-1, "%s: q_offset %d + Sq %d > Skv %d (a query without a key slot of its own)", fn, (int)q_offset,
-                    (int)Sq, Skv);
-    if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
-    if (key_mask && key_mask_ld < (Skv + 63) / 64)
-        return fail(-1, "%s: key_mask_ld %lld < ceil(Skv / 64)", fn, (long long)key_mask_ld);
-    const int nsplit = num_splits ? num_splits : dec_default_splits(shape, Sq);
-    if (nsplit > 65535) return fail(-1, "%s: num_splits = %d is above 65535", fn, nsplit);
-    if (nsplit > 1 && !workspace)
-        return fail(-1, "%s: null workspace with %d splits (smt_attn_cached_workspace bytes)", fn, nsplit);
-    if (nsplit > 1 && !al16(workspace)) return fail(-2, "%s: workspace needs 16-byte alignment", fn);
-    const int kv_all = q_offset + Sq;                      // keys any query of the call sees: [0, kv_all)
-    if ((int64_t)kv_all * k->ss * 2 >= 0x7fffffffLL || (int64_t)kv_all * v->ss * 2 >= 0x7fffffffLL)
-        return fail(-2, "%s: the visible K / V rows of one head must span less than 2 GiB", fn);
-    const int64_t ncols = (int64_t)Sq * (shape->Hq / shape->Hkv);
-    const int64_t bh = (int64_t)shape->B * shape->Hkv;
-    if (ncols > 0x7fffffffLL / 2 || bh > 65535) return fail(-1, "%s: B * Hkv must stay within 65535 and Sq * G below 2^30", fn);
-    DecArgs a;
-    a.q = tns(q); a.k = tns(k); a.v = tns(v);
-    a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o->sb; a.o_sh = o->sh; a.o_ss = o->ss;
-    a.lse = lse;
-    a.kmask = key_mask; a.kmask_ld = key_mask_ld;
-    a.ws = static_cast<float*>(workspace);
-    a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.G = shape->Hq / shape->Hkv;
-    a.Sq = Sq; a.q_offset = q_offset;
-    a.ncols = (int)ncols; a.ncb = dec_col_blocks(shape, Sq); a.nsplit = nsplit;
-    const int tiles = (kv_all + kKV - 1) / kKV;
-    a.tps = (tiles + nsplit - 1) / nsplit;
-    a.sl2 = shape->scale * 1.4426950408889634f;
-    const dim3 grid((unsigned)a.ncb, (unsigned)nsplit, (unsigned)bh);
-    if (shape->dtype == SMT_DTYPE_FP16) SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_FP16, key_mask, nsplit == 1, grid, stream, a);
-    else SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_BF16, key_mask, nsplit == 1, grid, stream, a);
-    if ((rc = check_launch("attn_decode_kernel")) || nsplit == 1) return rc;
-    const dim3 cgrid((unsigned)ncols, (unsigned)bh);
-    if (shape->dtype == SMT_DTYPE_FP16)
-        hipLaunchKernelGGL(attn_decode_combine_kernel<SMT_DTYPE_FP16>, cgrid, dim3(kD), 0, stream, a);
-    else hipLaunchKernelGGL(attn_decode_combine_kernel<SMT_DTYPE_BF16>, cgrid, dim3(kD), 0, stream, a);
-    return check_launch("attn_decode_combine_kernel");
+    return attn_fwd_cached("smt_attn_fwd_cached", q, k, v, o, lse, key_mask, key_mask_ld, Sq, q_offset, nullptr, 0, false,
+                           num_splits, workspace, shape, stream);
+}
+
+int smt_attn_fwd_cached_pos(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
+                            const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
+                            int32_t Sq, const int64_t* positions, int32_t positions_stride, int32_t num_splits,
+                            void* workspace, const smt_attn_shape* shape, hipStream_t stream) {
+    return attn_fwd_cached("smt_attn_fwd_cached_pos", q, k, v, o, lse, key_mask, key_mask_ld, Sq, 0, positions,
+                           positions_stride, true, num_splits, workspace, shape, stream);
 }
 
 }  // extern "C"

@@ -1017,15 +1017,36 @@ def flash_attention(q, k, v, scale=None, key_mask: "KeyMask" = None, joint: bool
 class CacheMask:
     """What :func:`smt_flash_mask` returns for a call against a KV cache: ``key_mask`` (a
     :class:`KeyMask` over the ``kv_length`` cached keys, or None), the absolute position ``q_offset``
-    of the call's first query and ``kv_length``."""
+    of the call's first query and ``kv_length``. ``q_offset`` is an int, or, for a decode step on a
+    static cache, an integer tensor that stays on its device (``flash_attention_cached`` hands it to
+    the kernel). ``prefill``: None, or, for the first forward on a static cache (offset 0, fewer
+    queries than key slots), the mask of the same-length call over the first ``q_length`` keys as a
+    one-element tuple (a :class:`KeyMask` or None), which the training forward kernel then runs."""
 
-    __slots__ = ("key_mask", "q_offset", "kv_length")
+    __slots__ = ("key_mask", "q_offset", "kv_length", "prefill")
 
-    def __init__(self, key_mask, q_offset: int, kv_length: int):
-        self.key_mask, self.q_offset, self.kv_length = key_mask, int(q_offset), int(kv_length)
+    def __init__(self, key_mask, q_offset, kv_length: int, prefill=None):
+        self.key_mask, self.kv_length, self.prefill = key_mask, int(kv_length), prefill
+        self.q_offset = q_offset if isinstance(q_offset, torch.Tensor) else int(q_offset)
 
 
-def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_offset: int = None,
+def _device_positions(t: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """A tensor-valued ``q_offset`` as the kernel reads it: int64, one element or one per batch row,
+    on q's device. int64 is used in place; int32 (or a strided ``[B]``) costs one device op. Nothing
+    here reads a value."""
+    if t.device != q.device:
+        raise ValueError(f"cached flash attention: q_offset tensor on {t.device}, q on {q.device}")
+    if t.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"cached flash attention: q_offset tensor of dtype {t.dtype} (int64 or int32)")
+    if t.dim() > 1 or t.numel() not in (1, q.shape[0]):
+        raise ValueError(f"cached flash attention: q_offset tensor of shape {tuple(t.shape)} (0-d, [1] or "
+                         f"[{q.shape[0]}])")
+    if t.dtype != torch.int64:
+        t = t.to(torch.int64)
+    return t if t.numel() == 1 or t.stride(0) == 1 else t.contiguous()
+
+
+def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_offset=None,
                            num_splits: int = None, return_lse: bool = False):
     """Attention of ``Sq`` new positions against a KV cache, forward only (``smt_attn_fwd_cached``, the
     split-KV decode kernel): q ``[B, Hq, Sq, 128]``, k / v ``[B, Hkv, Skv, 128]`` (any strides with
@@ -1033,6 +1054,12 @@ def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_of
     ``[B, Sq, Hq, 128]``. Query i sits at position ``q_offset + i`` (default ``Skv - Sq``: the queries
     are the last positions) and sees key j iff ``j <= q_offset + i`` and ``key_mask`` (over the Skv
     keys) keeps j; K / V rows at ``q_offset + Sq`` and later are never read. Any ``Skv``.
+    ``q_offset`` may be an integer tensor on q's device, 0-d, ``[1]`` or ``[B]`` (one position per
+    batch row): the kernel reads it (``smt_attn_fwd_cached_pos``), the host never does, so the call
+    can be captured in a graph and replayed while the tensor changes; ``Skv`` is then the capacity of
+    the buffers, the split count and the workspace follow the capacity, and a value outside
+    ``[0, Skv - Sq]`` is saturated into it by the kernel. For a given ``num_splits`` the result equals
+    the integer call's bit for bit.
     ``num_splits``: how many workgroups share one (batch, kv head)'s key range (None: the library's
     default for the shape); the result is bit-reproducible for a given value. ``return_lse``: also
     return the fp32 ``[B, Hq, Sq]`` log-sum-exp (log2 units, include/smt_attention.h). The workspace
@@ -1051,9 +1078,15 @@ def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_of
     if D != 128 or k.shape != (B, Hkv, Skv, D) or Hq % Hkv or Sq < 1:
         raise NotImplementedError(f"cached flash attention: head_dim 128, Hq % Hkv == 0, Sq >= 1 "
                                   f"(q {tuple(q.shape)}, k {tuple(k.shape)})")
-    q_offset = Skv - Sq if q_offset is None else int(q_offset)
-    if q_offset < 0 or q_offset + Sq > Skv:
-        raise ValueError(f"cached flash attention: queries at positions [{q_offset}, {q_offset + Sq}) of {Skv} key slots")
+    pos = None
+    if isinstance(q_offset, torch.Tensor):
+        pos, q_offset = _device_positions(q_offset, q), None
+        if Sq > Skv:
+            raise ValueError(f"cached flash attention: {Sq} query positions against {Skv} key slots")
+    else:
+        q_offset = Skv - Sq if q_offset is None else int(q_offset)
+        if q_offset < 0 or q_offset + Sq > Skv:
+            raise ValueError(f"cached flash attention: queries at positions [{q_offset}, {q_offset + Sq}) of {Skv} key slots")
     num_splits = 0 if num_splits is None else int(num_splits)
     if num_splits < 0:
         raise ValueError(f"cached flash attention: num_splits = {num_splits}")
@@ -1077,12 +1110,15 @@ def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_of
     ws_bytes = lib.smt_attn_cached_workspace(ctypes.byref(shape), Sq, num_splits)
     _hip._check(min(ws_bytes, 0), "smt_attn_cached_workspace")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes else None
+    tensors = (ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)), ctypes.byref(_attn_tensor(v)),
+               ctypes.byref(_attn_tensor(o.transpose(1, 2))), lse.data_ptr() if lse is not None else None, km, km_ld)
+    tail = (num_splits, ws.data_ptr() if ws is not None else None, ctypes.byref(shape), _stream(q))
     with torch.cuda.device(q.device):
-        rc = lib.smt_attn_fwd_cached(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
-                                     ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(o.transpose(1, 2))),
-                                     lse.data_ptr() if lse is not None else None, km, km_ld, Sq, q_offset, num_splits,
-                                     ws.data_ptr() if ws is not None else None, ctypes.byref(shape), _stream(q))
-    _hip._check(rc, "smt_attn_fwd_cached")
+        if pos is not None:
+            rc = lib.smt_attn_fwd_cached_pos(*tensors, Sq, pos.data_ptr(), 0 if pos.numel() == 1 else 1, *tail)
+        else:
+            rc = lib.smt_attn_fwd_cached(*tensors, Sq, q_offset, *tail)
+    _hip._check(rc, "smt_attn_fwd_cached_pos" if pos is not None else "smt_attn_fwd_cached")
     return (o, lse) if return_lse else o
 
 
@@ -1096,7 +1132,10 @@ def smt_flash_attention_forward(module, query, key, value, attention_mask, dropo
 
     A call against a KV cache (a :class:`CacheMask` from :func:`smt_flash_mask`, or fewer queries than
     keys) runs :func:`flash_attention_cached`, forward only: dropout or a :class:`DocMask` with a
-    cache raises. Every same-length call goes to :func:`flash_attention` with ``any_length=True``: the
+    cache raises. A tensor ``q_offset`` in the :class:`CacheMask` (a decode step on a static cache) is
+    passed through to the kernel; the first forward on a static cache (``CacheMask.prefill``) runs the
+    training forward kernel on the first ``Sq`` rows of the buffer.
+    Every same-length call goes to :func:`flash_attention` with ``any_length=True``: the
     reference's collator pads a batch to its longest sample (helper.py:191-205), so S is any integer in
     training, in the evaluation loss and in the prefill of ``generate()``. A gradient-free call takes
     that route too: at B 16, Hq 32, Hkv 8 the training forward measured 3.3-3.7x (S 2047) and 2.1x
@@ -1121,6 +1160,11 @@ def smt_flash_attention_forward(module, query, key, value, attention_mask, dropo
                 raise ValueError(f"smt_flash attention: mask built for {attention_mask.kv_length} cached keys, the "
                                  f"cache holds {Skv}")
             km, q_offset = attention_mask.key_mask, attention_mask.q_offset
+            if attention_mask.prefill is not None and Sq < Skv:
+                # the prefill on a static cache: the first Sq slots hold this call's keys, the rest
+                # are behind the causal edge; the training forward as for the DynamicCache prefill
+                return flash_attention(query, key[:, :, :Sq], value[:, :, :Sq], scaling, attention_mask.prefill[0],
+                                       any_length=True), None
         return flash_attention_cached(query, key, value, scaling, km, q_offset), None
     # the engine marks attention modules whose q/k/v_proj share a joint transposed copy
     docs = attention_mask if isinstance(attention_mask, DocMask) else None
@@ -1169,9 +1213,13 @@ def smt_flash_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mas
     length and the 2-D ``attention_mask`` (of a left-padded batch) as a :class:`KeyMask` over the
     ``kv_length`` keys, built without a host synchronisation (nothing asks whether every key is valid:
     this runs once per generated token).
-    Anything the kernels do not implement (``kv_offset != 0``, sliding windows, custom mask
-    functions, packed rows together with a cache, a tensor-valued ``q_offset`` of a static cache
-    under ``torch.compile``) raises."""
+    A static cache (``cache_implementation="static"``) hands over its fill level as a device tensor
+    and a mask over the keys written so far, shorter than the buffer. At ``q_length == 1`` the
+    :class:`CacheMask` carries a copy of that tensor and nothing reads it on the host; at
+    ``q_length > 1`` (the prefill, once per ``generate()``) it is read once. The short mask is
+    extended to the buffer with tensor ops; the slots beyond it are behind the causal edge.
+    Anything the kernels do not implement (``kv_offset != 0`` or tensor-valued, sliding windows,
+    custom mask functions, packed rows together with a cache) raises."""
     from transformers.masking_utils import causal_mask_function
     packed_ids = None
     if mask_function is not None and mask_function is not causal_mask_function:
@@ -1179,24 +1227,51 @@ def smt_flash_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mas
         if packed_ids is None:
             raise NotImplementedError("smt_flash attention: custom mask functions are not supported (causal, or "
                                       "causal AND transformers' packed-sequence mask)")
-    if isinstance(q_offset, torch.Tensor) or isinstance(kv_offset, torch.Tensor):
-        raise NotImplementedError("smt_flash attention: tensor-valued cache offsets (a static cache under "
-                                  "torch.compile) are not supported; use the default DynamicCache")
+    if isinstance(kv_offset, torch.Tensor):
+        raise NotImplementedError("smt_flash attention: a tensor-valued kv_offset (a sliding or offset cache) is not "
+                                  "supported")
     if kv_offset:
         raise NotImplementedError("smt_flash attention: kv_offset != 0 (a sliding or offset cache) is not supported")
-    if q_offset or q_length != kv_length:
+    static = isinstance(q_offset, torch.Tensor)           # a static cache's fill level, on its device
+    if static:
+        if q_offset.numel() != 1 or q_offset.dtype not in (torch.int64, torch.int32):
+            raise NotImplementedError(f"smt_flash attention: a tensor q_offset is one int64 / int32 element, got "
+                                      f"{q_offset.dtype} {tuple(q_offset.shape)}")
+        if q_length == 1:
+            # A decode step: the kernel reads the position. A copy, because the cache advances its
+            # counter in place before the attention of this forward runs.
+            q_offset = q_offset.clone()
+        else:
+            q_offset = int(q_offset)                      # the prefill: one host read per forward
+    if static or q_offset or q_length != kv_length:
         if packed_ids is not None:
             raise NotImplementedError("smt_flash attention: packed rows together with a KV cache are not supported")
-        if q_offset < 0 or q_offset + q_length > kv_length:
+        if not isinstance(q_offset, torch.Tensor) and (q_offset < 0 or q_offset + q_length > kv_length):
             raise NotImplementedError(f"smt_flash attention: queries [{q_offset}, {q_offset + q_length}) do not fit "
                                       f"{kv_length} cached keys")
-        km = None
+        km, short = None, False
         if attention_mask is not None:
             am = attention_mask
-            if am.dim() != 2 or am.shape[0] != batch_size or am.shape[1] < kv_length:
+            if am.dim() != 2 or am.shape[0] != batch_size:
                 raise NotImplementedError(f"smt_flash attention: 2-D [B, S] padding mask expected, got {tuple(am.shape)}")
+            short = am.shape[1] < kv_length
+            if short:
+                # A static cache: the mask covers the q_offset + q_length keys written so far, the
+                # buffer more. The slots beyond it are behind the causal edge whatever their bits say.
+                if isinstance(q_offset, int) and am.shape[1] < q_offset + q_length:
+                    raise NotImplementedError(f"smt_flash attention: padding mask over {am.shape[1]} keys, queries up "
+                                              f"to position {q_offset + q_length}")
+                am = torch.nn.functional.pad(am, (0, kv_length - am.shape[1]))
             km = KeyMask.from_padding_mask(am[:, :kv_length])
-        return CacheMask(km, q_offset, kv_length)
+        prefill = None
+        if 1 < q_length < kv_length and (static or short) and q_offset == 0:
+            # the first forward on a static cache: a same-length call on the first q_length slots
+            pm = None
+            if attention_mask is not None:
+                pm = attention_mask[:, :q_length].to(torch.bool)
+                pm = None if bool(pm.all()) else KeyMask.from_padding_mask(pm)
+            prefill = (pm,)
+        return CacheMask(km, q_offset, kv_length, prefill)
     if packed_ids is not None:
         if attention_mask is not None:
             raise NotImplementedError(_DOC_AND_KEY_MASK)
@@ -1243,6 +1318,11 @@ def eager_apply_rotary_pos_emb(*a, **k):
     return _ml() and _EAGER["rope"](*a, **k)
 
 
+def _keep_2d_mask(config=None, inputs_embeds=None, attention_mask=None, **kwargs):
+    """``create_masks_for_generate`` of a patched model: the 2-D padding mask as it came."""
+    return attention_mask
+
+
 def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_head_loss: bool = None) -> dict:
     """Route a transformers LLaMA model's RMSNorm / RoPE / SwiGLU / attention-residual add (and, with ``attention``, its
     attention; with ``loss``, its causal-LM loss) through the fused kernels. RoPE is patched at
@@ -1251,6 +1331,9 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
     ``smt_flash``; the loss through the model's ``loss_function`` attribute. ``lm_head_loss``
     (default: ``SMT_LM_HEAD_LOSS``, on): with ``loss``, the model's forward runs the LM head and the
     loss together, chunk by chunk, without the full logits (:func:`fused_causal_lm_forward`).
+    With ``attention``, ``generation_config.disable_compile`` is set and the model keeps the 2-D mask
+    in ``generate()`` (``create_masks_for_generate``), so that ``cache_implementation="static"`` runs
+    the kernels eagerly; :func:`unpatch_llama` restores both.
     Returns counts of patched modules. Idempotent."""
     ml = _ml()
     counts = {"rmsnorm": 0, "mlp": 0, "rope": 1, "attention": 0, "loss": 0, "decoder": 0, "lm_head_loss": 0}
@@ -1270,6 +1353,17 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
             _EAGER["smt_prev_attn"] = cfg._attn_implementation
         cfg._attn_implementation = register_attention()
         counts["attention"] = sum(1 for m in model.modules() if isinstance(m, ml.LlamaAttention))
+        # generate() sends a static cache on a GPU through torch.compile unless told otherwise, and
+        # torch.compile cannot trace the ctypes launches
+        gen = getattr(model, "generation_config", None)
+        if gen is not None and "_smt_prev_disable_compile" not in model.__dict__:
+            model.__dict__["_smt_prev_disable_compile"] = getattr(gen, "disable_compile", False)
+            gen.disable_compile = True
+        if gen is not None:
+            # ... and, for a compilable cache, builds the mask before the forward and passes the
+            # result in place of the 2-D mask; only a 4-D tensor survives that. Keep the 2-D mask:
+            # the forward builds the CacheMask itself, as with a DynamicCache.
+            model.__dict__["create_masks_for_generate"] = _keep_2d_mask
     for m in model.modules():
         if isinstance(m, ml.LlamaRMSNorm):
             m.forward = fused_rmsnorm_forward.__get__(m, type(m))
@@ -1299,6 +1393,12 @@ def unpatch_llama(model: nn.Module = None) -> None:
     if model is not None and "smt_prev_attn" in _EAGER and getattr(model, "config", None) is not None:
         model.config._attn_implementation = _EAGER.pop("smt_prev_attn")
     if model is not None:
+        if "_smt_prev_disable_compile" in model.__dict__:
+            prev = model.__dict__.pop("_smt_prev_disable_compile")
+            if getattr(model, "generation_config", None) is not None:
+                model.generation_config.disable_compile = prev
+        if model.__dict__.get("create_masks_for_generate") is _keep_2d_mask:
+            del model.__dict__["create_masks_for_generate"]
         if "_loss_function" in model.__dict__:
             del model.__dict__["_loss_function"]
         if "forward" in model.__dict__:
