@@ -57,7 +57,8 @@ int smt_rmsnorm_bwd_add(const void* dy, int64_t ld_dy, const void* x, int64_t ld
 /* Number of waves (and rows of dw_partial) smt_rmsnorm_bwd uses for `rows` rows. */
 int smt_rmsnorm_bwd_waves(int64_t rows);
 
-/* dx (and, if dw != NULL, dw via dw_partial[smt_rmsnorm_bwd_waves(rows)][hidden] fp32). */
+/* dx (and, if dw != NULL, dw via dw_partial[smt_rmsnorm_bwd_waves(rows)][hidden] fp32), for any
+ * hidden % 8 == 0. */
 int smt_rmsnorm_bwd(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, const void* weight, const float* rstd,
                     void* dx, int64_t ld_dx, float* dw_partial, void* dw, int64_t rows, int32_t hidden,
                     int32_t dtype, hipStream_t stream);

@@ -47,9 +47,16 @@ template <int F> __device__ __forceinline__ float u2f(uint32_t b16) {         //
     if constexpr (F == SMT_DTYPE_FP16) return (float)__builtin_bit_cast(_Float16, (uint16_t)b16);
     else return __uint_as_float(b16 << 16);
 }
+// For fp16 the fp32 value passes an empty asm first: hipcc otherwise folds the multiply or fma that
+// produced it into the conversion (v_fma_mixlo_f16: one rounding of the exact result), where the eager
+// chain rounds to fp32 and then to fp16. The two differ when the fp32 value lands on an fp16 tie
+// (about 1e-4 of the elements of x * rstd; smt_rmsnorm_bwd_add then differed from smt_rmsnorm_bwd plus
+// the add at CPL 9, where only some of the stores were folded).
 template <int F> __device__ __forceinline__ uint32_t f2u(float f) {           // fp32 -> 16-bit bits (RNE)
-    if constexpr (F == SMT_DTYPE_FP16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
-    else return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
+    if constexpr (F == SMT_DTYPE_FP16) {
+        asm("" : "+v"(f));
+        return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+    } else return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
 }
 // round through F. For fp16 the rounded bits pass an empty asm: hipcc otherwise shrinks
 // float(half(a * b)) + c to a half multiply and contracts it with the add into v_pk_fma_f16, dropping
@@ -155,6 +162,15 @@ void rmsnorm_fwd_kernel(const uint16_t* __restrict__ x, int64_t ldx, const uint1
     }
 }
 
+// r * gw - x * coef. For fp16 the contraction is spelled out (x * coef rounded to fp32, then one fma, which
+// is what the bf16 instances compile to): left to hipcc, the fp16 instances contracted some elements
+// of a row and not others (v_fma_mix_f32 beside v_mul_f32 + v_sub_f32), differently in each instance,
+// so that smt_rmsnorm_bwd_add was not smt_rmsnorm_bwd plus the add bit for bit.
+template <int F> __device__ __forceinline__ float dx_pre(float r, float gw, float x, float coef) {
+    if constexpr (F == SMT_DTYPE_FP16) return __builtin_fmaf(r, gw, -(x * coef));
+    else return r * gw - x * coef;
+}
+
 // Backward of the eager chain: dn = bf16(dy * w); dx = bf16(r*dn - xf * r^3 * sum(dn*xf) / H), for
 // any hidden % 8 == 0 (the register-resident kernels below cover hidden % 512 == 0). Waves stride
 // over rows.
@@ -184,7 +200,7 @@ void rmsnorm_bwd_kernel(const uint16_t* __restrict__ dy, int64_t lddy, const uin
             const F8 xv = ld8<F>(xr + c * 8), gv = ld8<F>(dyr + c * 8), wv = ld8<F>(w + c * 8);
             F8 o;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o.v[j] = r * rnd<F>(gv.v[j] * wv.v[j]) - xv.v[j] * coef;
+            for (int j = 0; j < 8; ++j) o.v[j] = dx_pre<F>(r, rnd<F>(gv.v[j] * wv.v[j]), xv.v[j], coef);
             st8<F>(dxr + c * 8, o);
         }
     }
@@ -347,7 +363,7 @@ void rmsnorm_bwd_reg_kernel(const uint16_t* __restrict__ dy, int64_t lddy, const
         const F8 xv = RowReg<PACK, F>::get(xr[k]), gw = RowReg<PACK, F>::get(gr[k]);
         F8 o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o.v[j] = r * gw.v[j] - xv.v[j] * coef;
+        for (int j = 0; j < 8; ++j) o.v[j] = dx_pre<F>(r, gw.v[j], xv.v[j], coef);
         if (ADD) {
             F8 dr;
             if constexpr (PRE) dr = unpack8<F>(drr[k]);
@@ -767,9 +783,20 @@ template <int F>
 int launch_bwd_dw(const void* dres, int64_t lddr, const void* dy, int64_t lddy, const void* x, int64_t ldx,
                   const void* w, const float* rstd, void* dx, int64_t lddx, float* dw_partial, void* dw, int64_t rows,
                   int H, hipStream_t stream) {
-    if (!dw_partial || !dw || (H % 512) || H > 8192)
-        return fail(-1, "smt_rmsnorm_bwd: weight grad needs hidden %% 512 == 0, <= 8192 and a partial buffer");
-    int rc = launch_bwd_reg<F>(dres != nullptr, dy, lddy, x, ldx, w, rstd, dres, lddr, dx, lddx, rows, H, stream);
+    if (!dw_partial || !dw) return fail(-1, "smt_rmsnorm_bwd: weight grad needs a partial buffer");
+    const bool reg = H % 512 == 0 && H <= 8192;
+    if (!reg && dres)
+        return fail(-1, "smt_rmsnorm_bwd_add_dw: hidden %d must be a multiple of 512, <= 8192", H);
+    int rc;
+    if (reg) {
+        rc = launch_bwd_reg<F>(dres != nullptr, dy, lddy, x, ldx, w, rstd, dres, lddr, dx, lddx, rows, H, stream);
+    } else {
+        // any other hidden % 8 == 0: dx by the generic kernel; the dw kernels below take any such size
+        hipLaunchKernelGGL(rmsnorm_bwd_kernel<F>, dim3(smt_rmsnorm_bwd_waves(rows) / 4), dim3(256), 0, stream,
+                           (const uint16_t*)dy, lddy, (const uint16_t*)x, ldx, (const uint16_t*)w, rstd, (uint16_t*)dx,
+                           lddx, rows, H);
+        rc = check_launch("rmsnorm_bwd_kernel");
+    }
     if (rc) return rc;
     const int64_t cap = smt_rmsnorm_bwd_waves(rows);
     int64_t per = (rows + cap - 1) / cap;

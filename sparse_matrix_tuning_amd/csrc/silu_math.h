@@ -6,6 +6,14 @@
 // the tests bound (tests/test_gpu_fused_llama.py, <= 1e-3 of the values one bf16 step apart).
 #pragma once
 
+// v_rcp_f32 returns zero where its result would be denormal (e > 2^126, x below about -87.3), while
+// the eager sigmoid keeps the denormal until exp overflows (x < -88.7); with an infinite incoming
+// gradient the backward then gave 0 * inf = NaN where eager gives inf. There the reciprocal is taken
+// of e * 2^-64 + 1 (the 1 is far below half a step of either sum there) and scaled back by a multiply,
+// which keeps denormals; elsewhere k = 1, and fma(e, 1, 1) and the multiply by 1 are the same values
+// as before. No branch.
 __device__ __forceinline__ float smt_sigmoid(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-x * 1.4426950408889634f));
+    const float e = __builtin_amdgcn_exp2f(-x * 1.4426950408889634f);
+    const float k = e > 0x1p126f ? 0x1p-64f : 1.0f;
+    return __builtin_amdgcn_rcpf(__builtin_fmaf(e, k, 1.0f)) * k;
 }

@@ -95,6 +95,12 @@ class FusedRMSNormFn(torch.autograd.Function):
         return dx.view(ctx.shape), dw, None
 
 
+def _reg_hidden(H: int) -> bool:
+    """The register-resident norm kernels (a row of 512 * k values per wave, k <= 16) take this hidden
+    size; every other hidden % 8 == 0 runs the generic kernels, which have no fused residual add."""
+    return H % 512 == 0 and H <= 8192
+
+
 def _rmsnorm_bwd(x2, w, rstd, dy, need_dw: bool, dres=None):
     """dx (+ ``dres``, the gradient reaching the same input by the residual path) and, with
     ``need_dw``, the weight gradient. With both (the full fine-tuning warm-up) one
@@ -108,7 +114,7 @@ def _rmsnorm_bwd(x2, w, rstd, dy, need_dw: bool, dres=None):
         waves = lib.smt_rmsnorm_bwd_waves(rows)
         partial = torch.empty(waves, H, dtype=torch.float32, device=x2.device)
         dw = torch.empty(H, dtype=w.dtype, device=w.device)
-    if dres is not None and need_dw and H % 512 == 0 and H <= 8192:
+    if dres is not None and need_dw and _reg_hidden(H):
         dr2 = _rows2d(dres)
         rc = lib.smt_rmsnorm_bwd_add_dw(dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), w.data_ptr(),
                                         rstd.data_ptr(), dr2.data_ptr(), dr2.stride(0), dx.data_ptr(), dx.stride(0),
@@ -197,14 +203,22 @@ class FusedAddRMSNormFn(torch.autograd.Function):
             y = y.view(x.shape) if y is not None else x.new_zeros(()).expand(x.shape)
             y._smt_q8 = (y._version, q, sq)
             return h.view(x.shape), y
-        h = torch.empty((rows, H), dtype=x.dtype, device=x.device)
         y = torch.empty((rows, H), dtype=x.dtype, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         w = weight.contiguous()
-        rc = _hip.load().smt_add_rmsnorm_fwd(x2.data_ptr(), x2.stride(0), r2.data_ptr(), r2.stride(0), w.data_ptr(),
-                                             h.data_ptr(), H, y.data_ptr(), H, rstd.data_ptr(), rows, H, float(eps),
-                                             _dt(x), _stream(x))
-        _hip._check(rc, "smt_add_rmsnorm_fwd")
+        if _reg_hidden(H):
+            h = torch.empty((rows, H), dtype=x.dtype, device=x.device)
+            rc = _hip.load().smt_add_rmsnorm_fwd(x2.data_ptr(), x2.stride(0), r2.data_ptr(), r2.stride(0), w.data_ptr(),
+                                                 h.data_ptr(), H, y.data_ptr(), H, rstd.data_ptr(), rows, H, float(eps),
+                                                 _dt(x), _stream(x))
+            _hip._check(rc, "smt_add_rmsnorm_fwd")
+        else:
+            # the one-pass kernel holds a row in registers (hidden = 512 * k); any other hidden % 8 == 0:
+            # the model-dtype add, then the generic norm kernel over h (the same values)
+            h = (x2 + r2).contiguous()
+            rc = _hip.load().smt_rmsnorm_fwd(h.data_ptr(), H, w.data_ptr(), y.data_ptr(), H, rstd.data_ptr(), rows, H,
+                                             float(eps), _dt(x), _stream(x))
+            _hip._check(rc, "smt_rmsnorm_fwd")
         ctx.save_for_backward(h, w, rstd)
         ctx.shape = x.shape
         return h.view(x.shape), _tag(y.view(x.shape), _hip.RECOMPUTE_RMSNORM, h, None, w, rstd)
@@ -217,9 +231,10 @@ class FusedAddRMSNormFn(torch.autograd.Function):
         dw = None
         if dy is None:
             dx = dh
-        elif ctx.needs_input_grad[2] or dh is None:
-            # weight grad (full fine-tuning warm-up; the residual gradient added in the same pass)
-            # or no residual gradient: the plain norm backward
+        elif ctx.needs_input_grad[2] or dh is None or not _reg_hidden(H):
+            # weight grad (full fine-tuning warm-up; the residual gradient added in the same pass),
+            # no residual gradient, or a hidden size the one-pass kernel does not take: the plain
+            # norm backward
             dx, dw = _rmsnorm_bwd(h, w, rstd, dy, ctx.needs_input_grad[2], dh)
             dx = dx.view(ctx.shape)
         elif getattr(ctx, "quant_grad", False):

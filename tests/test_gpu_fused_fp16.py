@@ -31,7 +31,8 @@ def _rel(a, b):
 def _ulp_close(a, b, max_ulp_frac=1e-3):
     """fp16 tensors equal except for a small fraction differing by one rounding step (11 bits)."""
     a, b = a.float(), b.float()
-    bad = ((a - b).abs() > b.abs() * 2 ** -10 + 6e-8).float().mean().item()
+    # a NaN difference is not <= the tolerance: a NaN or Inf that b does not hold too counts as bad
+    bad = (~(((a - b).abs() <= b.abs() * 2 ** -10 + 6e-8) | (a == b))).float().mean().item()
     return bad <= max_ulp_frac, bad
 
 
