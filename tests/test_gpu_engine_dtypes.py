@@ -56,6 +56,8 @@ def test_adamw_tiles_write_the_parameter_dtype_into_w(pdt):
         ref.fused_adam_step(t_ref, g.cpu() * coef, m_ref, v_ref, step, 1e-3, (0.9, 0.95), 1e-8, 0.01)
     torch.cuda.synchronize()
     assert _rel(master, t_ref) < 1e-6
+    assert _rel(m, m_ref) < 1e-6
+    assert _rel(v, v_ref) < 1e-6
     assert torch.equal(param.cpu(), master.cpu().to(pdt))
     assert torch.equal(ref.gather_tiles(W.cpu(), tiles).reshape(-1), param.cpu())
     keep = torch.ones(3, 4, dtype=torch.bool)

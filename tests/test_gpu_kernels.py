@@ -198,6 +198,8 @@ def test_adamw_matches_oracle(tiled):
         ref.fused_adam_step(rp, g * coef, rm, rv, step, lr, betas, eps, wd)
     torch.cuda.synchronize()
     assert _rel(master, rp) < 1e-6
+    assert _rel(m, rm) < 1e-6
+    assert _rel(v, rv) < 1e-6
     assert torch.equal(param.cpu(), master.cpu().bfloat16())
     if tiled:
         tiles_now = ref.gather_tiles(W.cpu(), tile_list)
