@@ -1,10 +1,14 @@
-"""Per-kernel gfx950 ISA of one HIP source, for "this change leaves the existing kernels' code unchanged"
+r"""Per-kernel gfx950 ISA of one HIP source, for "this change leaves the existing kernels' code unchanged"
 checks (round 6: the 16-bit format templates of llama_kernels.hip / attn_kernels.hip).
 
     python scripts/diag/isa_compare.py dump <src.hip> <out.json>      # kernel -> normalised instructions
     python scripts/diag/isa_compare.py diff <before.json> <after.json> [--map OLD=NEW ...]
 
-``--re PATTERN=REPL`` applies a regular-expression substitution instead.
+``--re PATTERN=REPL`` applies a regular-expression substitution instead, e.g. for the ``_docs`` kernels
+folded into the plain templates as a fourth parameter ``DOC``:
+
+    --re '_docs_kernel<(\d), (true|false)>=_kernel<false, \1, \2, true>'
+    --re '(attn_(?:fwd|dq|dkdv)_kernel<(?:true|false), \d, (?:true|false))>=\1, false>'
 
 ``dump`` compiles the source to device assembly with the library's flags and keeps, per kernel
 symbol, its instruction lines with basic-block labels and comments stripped (labels are renumbered

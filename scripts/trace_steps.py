@@ -24,6 +24,7 @@ def cat(name):
         return "loss(smt_ce)"
     if n.startswith("Cijk") or n.startswith("Custom_Cijk"):
         return "gemm(hipBLASLt)"
+    # the packed-row (DOC) instances are instances of these templates too, so they fall into this bucket
     if "attn_fwd_kernel" in n or "attn_dq_kernel" in n or "attn_dkdv_kernel" in n or "attn_delta_kernel" in n:
         return "attention(smt_flash)"
     if any(k in n for k in ("rmsnorm", "rope_kernel", "swiglu")):

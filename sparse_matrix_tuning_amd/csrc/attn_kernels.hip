@@ -23,6 +23,12 @@
 //   chunk' = chunk ^ (((row & 3) << 2) | ((row >> 2) & 3))
 // which is conflict-free both for ds_read_b128 row reads (16 consecutive rows, same chunk) and for
 // ds_read_b64_tr_b16 transposed reads (4 consecutive rows land in 4 different 64-B quarters).
+//
+// Shared code is kept only where scripts/diag/isa_compare.py shows every kernel's instructions unchanged
+// (DESIGN §4a). Found to change code, so written out where they stand: a helper for the C-layout key
+// index of the mask loops; a shared workgroup -> (b, h, hk, q block) mapping of the forward / dQ
+// kernels; frag_or_zero in dQ and the decode kernel; store_row for dK / dV (as two row stores or per
+// 8-byte group) and for the decode output; the dQ first issue without its `nt > 0` test.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -172,6 +178,38 @@ __device__ __forceinline__ void pack_b_frags(const float (&p)[16], bf16x8_t& f0,
         if (h == 0) f0 = __builtin_bit_cast(bf16x8_t, v);
         else f1 = __builtin_bit_cast(bf16x8_t, v);
     }
+}
+
+// 8 consecutive d of one global row as a fragment; zeros for a row outside the tensor (never read).
+__device__ __forceinline__ bf16x8_t frag_or_zero(bool valid, const uint16_t* p) {
+    if (valid) return *reinterpret_cast<const bf16x8_t*>(p);
+    return __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
+}
+
+// One row of a C-layout accumulator (4 tiles of 32 d; the lane holds d = 32 dt + 8 g + 4 hi + 0..3),
+// scaled and rounded to the 16-bit format, as 8-byte stores.
+template <int F>
+__device__ __forceinline__ void store_row(uint16_t* row, const f32x16_t (&acc)[4], float s, int hi) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            uint2 w;
+            w.x = pk16<F>(acc[dt][4 * g] * s, acc[dt][4 * g + 1] * s);
+            w.y = pk16<F>(acc[dt][4 * g + 2] * s, acc[dt][4 * g + 3] * s);
+            const int d = 32 * dt + 8 * g + 4 * hi;
+            *reinterpret_cast<uint2*>(row + d) = w;
+        }
+}
+
+// The lane constants of the explicit LDS reads (rowx / trx): row l32's 16-B chunk hi, and the
+// transposed reads' rows krow and krow + 4.
+__device__ __forceinline__ void lane_lds(int lane, int l32, int hi, uint32_t& lo_row, uint32_t& lo_t0, uint32_t& lo_t4) {
+    const uint32_t r = (uint32_t)l32;
+    lo_row = r * kRowB + ((16u * hi) ^ (swz(r) << 4));
+    const TrLane tl = tr_lane(lane);
+    lo_t0 = tl.krow * kRowB + (tl.feat_byte ^ (swz(tl.krow) << 4));
+    lo_t4 = (tl.krow + 4) * kRowB + (tl.feat_byte ^ (swz(tl.krow + 4) << 4));
 }
 
 // XCD-aware bijective remap (workgroups are dealt round-robin over the 8 XCDs): consecutive logical
@@ -390,6 +428,7 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
 // through tile<1>, so the ring slot stays a compile-time parity); a wave skips the compute, never the
 // DMA, wait or barrier, of tiles wholly before its own rows' smallest doc_start, tests key <
 // doc_start[q] on the tiles below its rows' largest doc_start, and runs the plain body on the rest.
+// The sweep is written once: in the plain instances its first tile t0 is the constant 0 and folds away.
 template <bool KMASK, int F, bool DROP, bool DOC = false>
 struct FwdLean {
     const FwdArgs& a;
@@ -557,8 +596,7 @@ struct FwdLean {
         if constexpr (DROP) drop_rk = drop_row_key(drop_head_key(*a.drop.seed, (uint32_t)(b * a.Hq + h)), (uint32_t)qrow);
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            if (qrow < a.S) qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + qrow * a.q.ss + 16 * ks + 8 * hi);
-            else qf[ks] = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
+            qf[ks] = frag_or_zero(qrow < a.S, qp + qrow * a.q.ss + 16 * ks + 8 * hi);
         }
         const int kv_end = min(a.S, q0 + kFwdQB);
         nt = (kv_end + kKV - 1) / kKV;
@@ -581,43 +619,24 @@ struct FwdLean {
             doc_wmax = wave_max(doc_ds);
             doc_t0 = wave_min(qvalid ? doc_ds : kIntMax) / kKV;        // a wave without a valid row: no tile
             t0 = doc_block_min(ds, q0, kFwdQB, a.S, lane) / kKV;       // <= q0 / kKV < nt (row q0 is valid)
-            issue(t0);
-        } else {
-            issue(0);
         }
+        issue(t0);
         vm_wait_all();
         vm_wait_all_known();                                   // the Q fragments too (compiler-visible)
         __syncthreads();
-        if constexpr (DOC) {
-            if (t0 & 1) {                                      // an odd first tile: once through slot 1
-                tile<1>(t0);
-                ++t0;
-            }
-            for (int t = t0; t < nt; t += 2) {
-                tile<0>(t);
-                if (t + 1 < nt) tile<1>(t + 1);
-            }
-        } else {
-            for (int t = 0; t < nt; t += 2) {
-                tile<0>(t);
-                if (t + 1 < nt) tile<1>(t + 1);
-            }
+        if (t0 & 1) {                                          // an odd first tile (DOC only): once through slot 1
+            tile<1>(t0);
+            ++t0;
+        }
+        for (int t = t0; t < nt; t += 2) {
+            tile<0>(t);
+            if (t + 1 < nt) tile<1>(t + 1);
         }
         const float l_tot = halves_sum(l_run);
         if (qrow < a.S) {
             float inv = (KMASK && !(l_tot > 0.f)) ? 0.f : 1.f / l_tot;
             if constexpr (DROP) inv *= a.drop.r;
-            uint16_t* op = a.o + b * a.o_sb + h * a.o_sh + (int64_t)qrow * a.o_ss;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = 32 * dt + 8 * g + 4 * hi;
-                    uint2 w;
-                    w.x = pk16<F>(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv);
-                    w.y = pk16<F>(o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-                    *reinterpret_cast<uint2*>(op + d) = w;
-                }
+            store_row<F>(a.o + b * a.o_sb + h * a.o_sh + (int64_t)qrow * a.o_ss, o, inv, hi);
             if (hi == 0)
                 a.lse[((int64_t)b * a.Hq + h) * a.lse_ld + qrow] =
                     (KMASK && !(l_tot > 0.f)) ? __builtin_huge_valf() : m_run + __log2f(l_tot);
@@ -625,9 +644,10 @@ struct FwdLean {
     }
 };
 
-template <bool KMASK, int F, bool DROP>
+template <bool KMASK, int F, bool DROP, bool DOC = false>
 __global__ __launch_bounds__(64 * kFwdWaves, 2)
 void attn_fwd_kernel(FwdArgs a) {
+    static_assert(!(KMASK && DOC), "no key mask beside documents");
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // K/V ring: 2 x 32 KiB
     const int nqb = (a.S + kFwdQB - 1) / kFwdQB;
     const int G = a.Hq / a.Hkv;
@@ -639,25 +659,7 @@ void attn_fwd_kernel(FwdArgs a) {
     const int grp = L / per_group;
     const int rem = L - grp * per_group;
     const int hk = grp % a.Hkv;
-    FwdLean<KMASK, F, DROP> fl(a, lds);
-    fl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
-}
-
-// The DOC instances are kernels of their own with attn_fwd_kernel's body, so the plain ones keep their
-// names and their code.
-template <int F, bool DROP>
-__global__ __launch_bounds__(64 * kFwdWaves, 2)
-void attn_fwd_docs_kernel(FwdArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // K/V ring: 2 x 32 KiB
-    const int nqb = (a.S + kFwdQB - 1) / kFwdQB;
-    const int G = a.Hq / a.Hkv;
-    const int total = nqb * a.Hq * a.B;
-    const int L = xcd_logical(blockIdx.x, total);              // the order of attn_fwd_kernel
-    const int per_group = G * nqb;
-    const int grp = L / per_group;
-    const int rem = L - grp * per_group;
-    const int hk = grp % a.Hkv;
-    FwdLean<false, F, DROP, true> fl(a, lds);
+    FwdLean<KMASK, F, DROP, DOC> fl(a, lds);
     fl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
 }
 
@@ -856,13 +858,7 @@ struct DqLean {
         rk = uniform_rsrc(kp, (int64_t)a.S * a.k.ss * 2);
         rv = uniform_rsrc(vp, (int64_t)a.S * a.v.ss * 2);
         lds0 = lds_addr(lds);
-        {
-            const uint32_t r = (uint32_t)l32;
-            lo_row = r * kRowB + ((16u * hi) ^ (swz(r) << 4));
-            const TrLane tl = tr_lane(lane);
-            lo_t0 = tl.krow * kRowB + (tl.feat_byte ^ (swz(tl.krow) << 4));
-            lo_t4 = (tl.krow + 4) * kRowB + (tl.feat_byte ^ (swz(tl.krow + 4) << 4));
-        }
+        lane_lds(lane, l32, hi, lo_row, lo_t0, lo_t4);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
@@ -874,47 +870,27 @@ struct DqLean {
             doc_wmax = wave_max(doc_ds);
             doc_t0 = wave_min(qvalid ? doc_ds : kIntMax) / kKV;        // a wave without a valid row: no tile
             t0 = doc_block_min(ds, q0, kDqQB, a.S, lane) / kKV;        // <= q0 / kKV < nt (row q0 is valid)
-            issue(t0);
-        } else {
-            if (nt > 0) issue(0);
         }
+        if (DOC || nt > 0) issue(t0);                          // nt > 0 always holds; the plain instances keep the test (header)
         vm_wait_all();
         vm_wait_all_known();
         __syncthreads();
-        if constexpr (DOC) {
-            if (t0 & 1) {                                      // an odd first tile: once through slot 1
-                tile<1>(t0);
-                ++t0;
-            }
-            for (int t = t0; t < nt; t += 2) {
-                tile<0>(t);
-                if (t + 1 < nt) tile<1>(t + 1);
-            }
-        } else {
-            for (int t = 0; t < nt; t += 2) {
-                tile<0>(t);
-                if (t + 1 < nt) tile<1>(t + 1);
-            }
+        if (t0 & 1) {                                          // an odd first tile (DOC only): once through slot 1
+            tile<1>(t0);
+            ++t0;
         }
-        if (qvalid) {
-            uint16_t* out = a.dq + b * a.dq_sb + h * a.dq_sh + (int64_t)qrow * a.dq_ss;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = 32 * dt + 8 * g + 4 * hi;
-                    uint2 w;
-                    w.x = pk16<F>(dq[dt][4 * g] * a.scale, dq[dt][4 * g + 1] * a.scale);
-                    w.y = pk16<F>(dq[dt][4 * g + 2] * a.scale, dq[dt][4 * g + 3] * a.scale);
-                    *reinterpret_cast<uint2*>(out + d) = w;
-                }
+        for (int t = t0; t < nt; t += 2) {
+            tile<0>(t);
+            if (t + 1 < nt) tile<1>(t + 1);
         }
+        if (qvalid) store_row<F>(a.dq + b * a.dq_sb + h * a.dq_sh + (int64_t)qrow * a.dq_ss, dq, a.scale, hi);
     }
 };
 
-template <bool KMASK, int F, bool DROP>
+template <bool KMASK, int F, bool DROP, bool DOC = false>
 __global__ __launch_bounds__(64 * kDqWaves, 8 / kDqWaves)
 void attn_dq_kernel(DqArgs a) {
+    static_assert(!(KMASK && DOC), "no key mask beside documents");
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // 64 KiB
     const int nqb = (a.S + kDqQB - 1) / kDqQB;
     const int G = a.Hq / a.Hkv;
@@ -926,23 +902,7 @@ void attn_dq_kernel(DqArgs a) {
     const int grp = L / per_group;
     const int rem = L - grp * per_group;
     const int hk = grp % a.Hkv;
-    DqLean<KMASK, F, DROP> dl(a, lds);
-    dl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
-}
-
-template <int F, bool DROP>
-__global__ __launch_bounds__(64 * kDqWaves, 8 / kDqWaves)
-void attn_dq_docs_kernel(DqArgs a) {                           // attn_dq_kernel's body with DOC
-    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // 64 KiB
-    const int nqb = (a.S + kDqQB - 1) / kDqQB;
-    const int G = a.Hq / a.Hkv;
-    const int total = nqb * a.Hq * a.B;
-    const int L = xcd_logical(blockIdx.x, total);
-    const int per_group = G * nqb;
-    const int grp = L / per_group;
-    const int rem = L - grp * per_group;
-    const int hk = grp % a.Hkv;
-    DqLean<false, F, DROP, true> dl(a, lds);
+    DqLean<KMASK, F, DROP, DOC> dl(a, lds);
     dl.run(grp / a.Hkv, hk * G + rem % G, hk, nqb - 1 - rem / G);
 }
 
@@ -1220,19 +1180,12 @@ struct DkvLean {
         const uint16_t* vp = a.v.p + b * a.v.sb + hk * a.v.sh;
         lds0 = lds_addr(lds);
         dma_rows(uniform_rsrc(vp, (int64_t)a.S * a.v.ss * 2), a.v.ss, lds0 + kDkvLeanRing * kSliceBuf, k0, kw, kKW / 4, lane);
-        {
-            const uint32_t r = (uint32_t)l32;
-            lo_row = r * kRowB + ((16u * hi) ^ (swz(r) << 4));
-            // V rows wave*32 + l32 (same swizzle as row l32), image after the ring (past the ds offset range)
-            lo_v = lo_row + (uint32_t)(kDkvLeanRing * kSliceBuf + wave * kKW * kRowB);
-            const TrLane tl = tr_lane(lane);
-            lo_t0 = tl.krow * kRowB + (tl.feat_byte ^ (swz(tl.krow) << 4));
-            lo_t4 = (tl.krow + 4) * kRowB + (tl.feat_byte ^ (swz(tl.krow + 4) << 4));
-        }
+        lane_lds(lane, l32, hi, lo_row, lo_t0, lo_t4);
+        // V rows wave*32 + l32 (same swizzle as row l32), image after the ring (past the ds offset range)
+        lo_v = lo_row + (uint32_t)(kDkvLeanRing * kSliceBuf + wave * kKW * kRowB);
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            if (key < a.S) kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + (int64_t)key * a.k.ss + 16 * ks + 8 * hi);
-            else kf[ks] = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
+            kf[ks] = frag_or_zero(key < a.S, kp + (int64_t)key * a.k.ss + 16 * ks + 8 * hi);
         }
         int s_end = a.S;
         if constexpr (DOC) {
@@ -1284,9 +1237,10 @@ struct DkvLean {
     }
 };
 
-template <bool KMASK, int F, bool DROP>
+template <bool KMASK, int F, bool DROP, bool DOC = false>
 __global__ __launch_bounds__(kDkvWaves * 64, 2)
 void attn_dkdv_kernel(DkvArgs a) {
+    static_assert(!(KMASK && DOC), "no key mask beside documents");
     __shared__ __attribute__((aligned(16))) uint8_t lds[kVImg + kDkvLeanRing * (kSliceBuf + (DROP ? kDropRkB : 0))];
     const int nkb = (a.S + kKB - 1) / kKB;
     const int total = ((nkb + 1) / 2) * a.Hkv * a.B;
@@ -1296,22 +1250,7 @@ void attn_dkdv_kernel(DkvArgs a) {
 #pragma nounroll
     for (int i = 0; i < t.n; ++i) {
         if (i) __syncthreads();
-        DkvLean<KMASK, F, DROP> dl(a, lds);
-        dl.run(t.b, t.hk, t.blk[1 - i]);
-    }
-}
-
-template <int F, bool DROP>
-__global__ __launch_bounds__(kDkvWaves * 64, 2)
-void attn_dkdv_docs_kernel(DkvArgs a) {                        // attn_dkdv_kernel's body with DOC
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kVImg + kDkvLeanRing * (kSliceBuf + (DROP ? kDropRkB : 0))];
-    const int nkb = (a.S + kKB - 1) / kKB;
-    const int total = ((nkb + 1) / 2) * a.Hkv * a.B;
-    const PairTask t = pair_task(xcd_logical(blockIdx.x, total), nkb, 1, a.Hkv);
-#pragma nounroll
-    for (int i = 0; i < t.n; ++i) {
-        if (i) __syncthreads();
-        DkvLean<false, F, DROP, true> dl(a, lds);
+        DkvLean<KMASK, F, DROP, DOC> dl(a, lds);
         dl.run(t.b, t.hk, t.blk[1 - i]);
     }
 }
@@ -1588,34 +1527,23 @@ int check_shape(const smt_attn_shape* s, const char* fn) {
     return 0;
 }
 
-// the (key mask, format, dropout) instance of a kernel template
-#define SMT_ATTN_LAUNCH_KD(kernel, F, kmask, drop, grid, block, stream, args)                                    \
-    do {                                                                                                      \
-        if (drop) {                                                                                           \
-            if (kmask) hipLaunchKernelGGL((kernel<true, F, true>), grid, block, 0, stream, args);            \
-            else hipLaunchKernelGGL((kernel<false, F, true>), grid, block, 0, stream, args);                 \
-        } else {                                                                                              \
-            if (kmask) hipLaunchKernelGGL((kernel<true, F, false>), grid, block, 0, stream, args);           \
-            else hipLaunchKernelGGL((kernel<false, F, false>), grid, block, 0, stream, args);                \
-        }                                                                                                     \
-    } while (0)
-#define SMT_ATTN_LAUNCH(kernel, kmask, dtype, drop, grid, block, stream, args)                                   \
-    do {                                                                                                      \
-        if ((dtype) == SMT_DTYPE_FP16) SMT_ATTN_LAUNCH_KD(kernel, SMT_DTYPE_FP16, kmask, drop, grid, block, stream, args); \
-        else SMT_ATTN_LAUNCH_KD(kernel, SMT_DTYPE_BF16, kmask, drop, grid, block, stream, args);             \
-    } while (0)
-
-// the (format, dropout) instance of a document-mask kernel
-#define SMT_ATTN_LAUNCH_DOCS(kernel, dtype, drop, grid, block, stream, args)                                     \
-    do {                                                                                                      \
-        if ((dtype) == SMT_DTYPE_FP16) {                                                                      \
-            if (drop) hipLaunchKernelGGL((kernel<SMT_DTYPE_FP16, true>), grid, block, 0, stream, args);      \
-            else hipLaunchKernelGGL((kernel<SMT_DTYPE_FP16, false>), grid, block, 0, stream, args);          \
-        } else {                                                                                              \
-            if (drop) hipLaunchKernelGGL((kernel<SMT_DTYPE_BF16, true>), grid, block, 0, stream, args);      \
-            else hipLaunchKernelGGL((kernel<SMT_DTYPE_BF16, false>), grid, block, 0, stream, args);          \
-        }                                                                                                     \
-    } while (0)
+// Picks a kernel instance: dispatch(dtype, fn, bools...) calls the generic lambda fn(f, c...) with the
+// format as a std::integral_constant and each runtime bool as a std::bool_constant, so f() and c() are
+// template arguments inside fn. A combination that has no instance (a key mask beside documents) is
+// fenced off with if constexpr there, and is never instantiated.
+template <class Fn>
+void with_bools(Fn&& fn) { fn(); }
+template <class Fn, class... Rest>
+void with_bools(Fn&& fn, bool b, Rest... rest) {
+    if (b) with_bools([&](auto... c) { fn(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { fn(std::false_type{}, c...); }, rest...);
+}
+template <class Fn, class... Bools>
+void dispatch(int dtype, Fn&& fn, Bools... bools) {
+    if (dtype == SMT_DTYPE_FP16)
+        with_bools([&](auto... c) { fn(std::integral_constant<int, SMT_DTYPE_FP16>{}, c...); }, bools...);
+    else with_bools([&](auto... c) { fn(std::integral_constant<int, SMT_DTYPE_BF16>{}, c...); }, bools...);
+}
 
 Tns tns(const smt_attn_tensor* t) { return Tns{static_cast<const uint16_t*>(t->ptr), t->sb, t->sh, t->ss}; }
 
@@ -1644,7 +1572,28 @@ struct DocArgs {
 };
 constexpr DocArgs kNoDocs = {nullptr, nullptr};
 
-// fn: the entry point's name for messages; drop.t == 0: the plain kernels; docs.start: the DOC kernels
+// the row stride of a key mask against the keys it has to cover (keys_name: "S" / "Skv" of the message)
+int check_kmask_ld(const char* fn, const uint64_t* key_mask, int64_t key_mask_ld, int keys, const char* keys_name) {
+    if (key_mask && key_mask_ld < (keys + 63) / 64)
+        return fail(-1, "%s: key_mask_ld %lld < ceil(%s / 64)", fn, (long long)key_mask_ld, keys_name);
+    return 0;
+}
+
+// the fields that FwdArgs, DqArgs and DkvArgs share
+template <class Args, class Lse>
+void fill_common(Args& a, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v, Lse* lse,
+                 int64_t lse_ld, const uint64_t* key_mask, int64_t key_mask_ld, DropArgs drop,
+                 const smt_attn_shape* shape) {
+    a.q = tns(q); a.k = tns(k); a.v = tns(v);
+    a.lse = lse; a.lse_ld = (int)lse_ld;
+    a.kmask = key_mask; a.kmask_ld = key_mask_ld;
+    a.B = shape->B; a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.S = shape->S;
+    a.sl2 = shape->scale * 1.4426950408889634f;
+    a.drop = drop;
+}
+
+// fn: the entry point's name for messages; drop.t == 0: the plain instances; docs.start: the DOC instances
+// (never beside a key mask: the *_docs entry points take none and check_ld refuses the pair)
 int attn_fwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
              const smt_attn_tensor* o, float* lse, int64_t lse_ld, const uint64_t* key_mask, int64_t key_mask_ld,
              DropArgs drop, DocArgs docs, const smt_attn_shape* shape, hipStream_t stream) {
@@ -1653,26 +1602,19 @@ int attn_fwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
         (rc = check_tensor(v, "v", fn)) || (rc = check_tensor(o, "o", fn)))
         return rc;
     if (!lse) return fail(-1, "%s: null lse", fn);
-    if (key_mask && key_mask_ld < (shape->S + 63) / 64)
-        return fail(-1, "%s: key_mask_ld %lld < ceil(S / 64)", fn, (long long)key_mask_ld);
+    if ((rc = check_kmask_ld(fn, key_mask, key_mask_ld, shape->S, "S"))) return rc;
     FwdArgs a;
-    a.q = tns(q); a.k = tns(k); a.v = tns(v);
+    fill_common(a, q, k, v, lse, lse_ld, key_mask, key_mask_ld, drop, shape);
     a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o->sb; a.o_sh = o->sh; a.o_ss = o->ss;
-    a.lse = lse; a.lse_ld = (int)lse_ld;
-    a.kmask = key_mask; a.kmask_ld = key_mask_ld;
-    a.B = shape->B; a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.S = shape->S;
-    a.sl2 = shape->scale * 1.4426950408889634f;
-    a.drop = drop;
     a.doc_start = docs.start;
     const int64_t nqb = (shape->S + kFwdQB - 1) / kFwdQB;
     const int64_t blocks = nqb * shape->Hq * shape->B;
     if (blocks > 0x7fffffffLL) return fail(-1, "%s: too many blocks", fn);
-    if (docs.start)
-        SMT_ATTN_LAUNCH_DOCS(attn_fwd_docs_kernel, shape->dtype, drop.t != 0, dim3((unsigned)blocks),
-                             dim3(64 * kFwdWaves), stream, a);
-    else
-        SMT_ATTN_LAUNCH(attn_fwd_kernel, key_mask, shape->dtype, drop.t != 0, dim3((unsigned)blocks),
-                        dim3(64 * kFwdWaves), stream, a);
+    dispatch(shape->dtype, [&](auto f, auto km, auto dr, auto doc) {
+        if constexpr (!(km() && doc()))
+            hipLaunchKernelGGL((attn_fwd_kernel<km(), f(), dr(), doc()>), dim3((unsigned)blocks), dim3(64 * kFwdWaves), 0,
+                               stream, a);
+    }, key_mask && !docs.start, drop.t != 0, docs.start != nullptr);
     return check_launch("attn_fwd_kernel");
 }
 
@@ -1690,43 +1632,44 @@ int attn_bwd(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k,
     // lse_ld == S from the entry points without a stride of their own (the *_ld ones refuse such a stride first)
     if (lse_ld & 3) return fail(-2, "%s: lse / delta need 16-byte rows (S %% 4 == 0; any S through smt_attn_bwd_ld)", fn);
     if (!al16(lse) || !al16(delta_ws)) return fail(-2, "%s: lse / delta need 16-byte aligned base pointers", fn);
-    if (key_mask && key_mask_ld < (shape->S + 63) / 64)
-        return fail(-1, "%s: key_mask_ld %lld < ceil(S / 64)", fn, (long long)key_mask_ld);
+    if ((rc = check_kmask_ld(fn, key_mask, key_mask_ld, shape->S, "S"))) return rc;
     const int B = shape->B, Hq = shape->Hq, Hkv = shape->Hkv, S = shape->S;
-    const float sl2 = shape->scale * 1.4426950408889634f;
-    const bool dropping = drop.t != 0;
+    const bool masked = key_mask && !docs.start, dropping = drop.t != 0, packed = docs.start != nullptr;
 
     DqArgs qa;
-    qa.q = tns(q); qa.k = tns(k); qa.v = tns(v); qa.dout = tns(d_o); qa.o = tns(o);
+    fill_common(qa, q, k, v, lse, lse_ld, key_mask, key_mask_ld, drop, shape);
+    qa.dout = tns(d_o); qa.o = tns(o);
     qa.dq = static_cast<uint16_t*>(dq->ptr); qa.dq_sb = dq->sb; qa.dq_sh = dq->sh; qa.dq_ss = dq->ss;
-    qa.lse = lse; qa.delta = delta_ws; qa.lse_ld = (int)lse_ld;
-    qa.kmask = key_mask; qa.kmask_ld = key_mask_ld;
-    qa.B = B; qa.Hq = Hq; qa.Hkv = Hkv; qa.S = S; qa.sl2 = sl2; qa.scale = shape->scale;
-    qa.drop = drop;
+    qa.delta = delta_ws; qa.scale = shape->scale;
     qa.doc_start = docs.start;
     const int64_t nqb = (S + kDqQB - 1) / kDqQB;
     const dim3 qgrid((unsigned)(nqb * Hq * B)), qblock(64 * kDqWaves);
-    if (docs.start) SMT_ATTN_LAUNCH_DOCS(attn_dq_docs_kernel, shape->dtype, dropping, qgrid, qblock, stream, qa);
-    else SMT_ATTN_LAUNCH(attn_dq_kernel, key_mask, shape->dtype, dropping, qgrid, qblock, stream, qa);
+    dispatch(shape->dtype, [&](auto f, auto km, auto dr, auto doc) {
+        if constexpr (!(km() && doc()))
+            hipLaunchKernelGGL((attn_dq_kernel<km(), f(), dr(), doc()>), qgrid, qblock, 0, stream, qa);
+    }, masked, dropping, packed);
     if ((rc = check_launch("attn_dq_kernel"))) return rc;
 
     DkvArgs ka;
-    ka.q = tns(q); ka.k = tns(k); ka.v = tns(v); ka.dout = tns(d_o);
+    fill_common(ka, q, k, v, lse, lse_ld, key_mask, key_mask_ld, drop, shape);
+    ka.dout = tns(d_o);
     ka.dk = static_cast<uint16_t*>(dk->ptr); ka.dk_sb = dk->sb; ka.dk_sh = dk->sh; ka.dk_ss = dk->ss;
     ka.dv = static_cast<uint16_t*>(dv->ptr); ka.dv_sb = dv->sb; ka.dv_sh = dv->sh; ka.dv_ss = dv->ss;
-    ka.lse = lse; ka.delta = delta_ws; ka.lse_ld = (int)lse_ld;
-    ka.kmask = key_mask; ka.kmask_ld = key_mask_ld;
-    ka.B = B; ka.Hq = Hq; ka.Hkv = Hkv; ka.S = S; ka.sl2 = sl2; ka.scale = shape->scale;
-    ka.drop = drop;
+    ka.delta = delta_ws; ka.scale = shape->scale;
     ka.doc_end = docs.end;
     const int64_t nkb = (S + kKB - 1) / kKB;
     const dim3 grid((unsigned)(((nkb + 1) / 2) * Hkv * B));
-    if (docs.start) SMT_ATTN_LAUNCH_DOCS(attn_dkdv_docs_kernel, shape->dtype, dropping, grid, dim3(kDkvWaves * 64), stream, ka);
-    else SMT_ATTN_LAUNCH(attn_dkdv_kernel, key_mask, shape->dtype, dropping, grid, dim3(kDkvWaves * 64), stream, ka);
+    dispatch(shape->dtype, [&](auto f, auto km, auto dr, auto doc) {
+        if constexpr (!(km() && doc()))
+            hipLaunchKernelGGL((attn_dkdv_kernel<km(), f(), dr(), doc()>), grid, dim3(kDkvWaves * 64), 0, stream, ka);
+    }, masked, dropping, packed);
     return check_launch("attn_dkdv_kernel");
 }
 
 constexpr DropArgs kNoDrop = {nullptr, 0u, 1.f};
+
+// lse_ld of the entry points without a stride of their own: S (a null shape is refused by attn_fwd / attn_bwd)
+int64_t own_ld(const smt_attn_shape* shape) { return shape ? shape->S : 0; }
 
 // what only the *_ld entry points can get wrong: the stride, and documents beside a key mask (the
 // shape itself is checked by attn_fwd / attn_bwd, a null one included)
@@ -1762,17 +1705,6 @@ int64_t dec_workspace(const smt_attn_shape* s, int32_t Sq, int32_t num_splits) {
     return (int64_t)s->B * s->Hkv * dec_col_blocks(s, Sq) * num_splits * kDecPartial * (int64_t)sizeof(float);
 }
 
-#define SMT_ATTN_LAUNCH_DEC(F, kmask, direct, Args, grid, stream, args)                                          \
-    do {                                                                                                      \
-        if (kmask) {                                                                                          \
-            if (direct) hipLaunchKernelGGL((attn_decode_kernel<true, F, true, Args>), grid, dim3(64), 0, stream, args);  \
-            else hipLaunchKernelGGL((attn_decode_kernel<true, F, false, Args>), grid, dim3(64), 0, stream, args);   \
-        } else {                                                                                              \
-            if (direct) hipLaunchKernelGGL((attn_decode_kernel<false, F, true, Args>), grid, dim3(64), 0, stream, args); \
-            else hipLaunchKernelGGL((attn_decode_kernel<false, F, false, Args>), grid, dim3(64), 0, stream, args);  \
-        }                                                                                                     \
-    } while (0)
-
 // smt_attn_fwd_cached (pos == nullptr: the position is q_offset) and smt_attn_fwd_cached_pos (the
 // position is read by the kernel; q_offset is unused and the bounds are taken on the capacity Skv).
 int attn_fwd_cached(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1798,8 +1730,7 @@ int attn_fwd_cached(const char* fn, const smt_attn_tensor* q, const smt_attn_ten
                         (int)Sq, Skv);
     }
     if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
-    if (key_mask && key_mask_ld < (Skv + 63) / 64)
-        return fail(-1, "%s: key_mask_ld %lld < ceil(Skv / 64)", fn, (long long)key_mask_ld);
+    if ((rc = check_kmask_ld(fn, key_mask, key_mask_ld, Skv, "Skv"))) return rc;
     const int nsplit = num_splits ? num_splits : dec_default_splits(shape, Sq);
     if (nsplit > 65535) return fail(-1, "%s: num_splits = %d is above 65535", fn, nsplit);
     if (nsplit > 1 && !workspace)
@@ -1825,22 +1756,19 @@ int attn_fwd_cached(const char* fn, const smt_attn_tensor* q, const smt_attn_ten
     a.tps = (tiles + nsplit - 1) / nsplit;                 // by_pos: the kernel's own, from its position
     a.sl2 = shape->scale * 1.4426950408889634f;
     const dim3 grid((unsigned)a.ncb, (unsigned)nsplit, (unsigned)bh);
-    if (by_pos) {
-        DecPosArgs ap;
-        static_cast<DecArgs&>(ap) = a;
-        ap.pos = pos; ap.pos_stride = pos_stride; ap.cap = Skv;
-        if (shape->dtype == SMT_DTYPE_FP16) SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_FP16, key_mask, nsplit == 1, DecPosArgs, grid, stream, ap);
-        else SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_BF16, key_mask, nsplit == 1, DecPosArgs, grid, stream, ap);
-    } else if (shape->dtype == SMT_DTYPE_FP16) {
-        SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_FP16, key_mask, nsplit == 1, DecArgs, grid, stream, a);
-    } else {
-        SMT_ATTN_LAUNCH_DEC(SMT_DTYPE_BF16, key_mask, nsplit == 1, DecArgs, grid, stream, a);
-    }
+    DecPosArgs ap;                                         // the device-position form of the same call
+    static_cast<DecArgs&>(ap) = a;
+    ap.pos = pos; ap.pos_stride = pos_stride; ap.cap = Skv;
+    dispatch(shape->dtype, [&](auto f, auto km, auto direct, auto pos_form) {
+        if constexpr (pos_form())
+            hipLaunchKernelGGL((attn_decode_kernel<km(), f(), direct(), DecPosArgs>), grid, dim3(64), 0, stream, ap);
+        else hipLaunchKernelGGL((attn_decode_kernel<km(), f(), direct(), DecArgs>), grid, dim3(64), 0, stream, a);
+    }, key_mask != nullptr, nsplit == 1, by_pos);
     if ((rc = check_launch("attn_decode_kernel")) || nsplit == 1) return rc;
     const dim3 cgrid((unsigned)ncols, (unsigned)bh);
-    if (shape->dtype == SMT_DTYPE_FP16)
-        hipLaunchKernelGGL(attn_decode_combine_kernel<SMT_DTYPE_FP16>, cgrid, dim3(kD), 0, stream, a);
-    else hipLaunchKernelGGL(attn_decode_combine_kernel<SMT_DTYPE_BF16>, cgrid, dim3(kD), 0, stream, a);
+    dispatch(shape->dtype, [&](auto f) {
+        hipLaunchKernelGGL(attn_decode_combine_kernel<f()>, cgrid, dim3(kD), 0, stream, a);
+    });
     return check_launch("attn_decode_combine_kernel");
 }
 
@@ -1854,7 +1782,7 @@ const char* smt_attn_last_error(void) { return g_err; }
 int smt_attn_fwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
                        const smt_attn_tensor* o, float* lse, const uint64_t* key_mask, int64_t key_mask_ld,
                        const smt_attn_shape* shape, hipStream_t stream) {
-    return attn_fwd(key_mask ? "smt_attn_fwd_kmask" : "smt_attn_fwd", q, k, v, o, lse, shape ? shape->S : 0, key_mask,
+    return attn_fwd(key_mask ? "smt_attn_fwd_kmask" : "smt_attn_fwd", q, k, v, o, lse, own_ld(shape), key_mask,
                     key_mask_ld, kNoDrop, kNoDocs, shape, stream);
 }
 
@@ -1869,7 +1797,7 @@ int smt_attn_bwd_kmask(const smt_attn_tensor* q, const smt_attn_tensor* k, const
                        const uint64_t* key_mask, int64_t key_mask_ld, const smt_attn_shape* shape,
                        hipStream_t stream) {
     return attn_bwd(key_mask ? "smt_attn_bwd_kmask" : "smt_attn_bwd", q, k, v, o, d_o, lse, delta_ws,
-                    shape ? shape->S : 0, dq, dk, dv, key_mask, key_mask_ld, kNoDrop, kNoDocs, shape, stream);
+                    own_ld(shape), dq, dk, dv, key_mask, key_mask_ld, kNoDrop, kNoDocs, shape, stream);
 }
 
 int smt_attn_bwd(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1888,7 +1816,7 @@ int smt_attn_fwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, con
     int rc;
     if ((rc = check_drop(p, seed, "smt_attn_fwd_dropout", &drop))) return rc;
     if (drop.t == 0) return smt_attn_fwd_kmask(q, k, v, o, lse, key_mask, key_mask_ld, shape, stream);
-    return attn_fwd("smt_attn_fwd_dropout", q, k, v, o, lse, shape ? shape->S : 0, key_mask, key_mask_ld, drop, kNoDocs,
+    return attn_fwd("smt_attn_fwd_dropout", q, k, v, o, lse, own_ld(shape), key_mask, key_mask_ld, drop, kNoDocs,
                     shape, stream);
 }
 
@@ -1902,7 +1830,7 @@ int smt_attn_bwd_dropout(const smt_attn_tensor* q, const smt_attn_tensor* k, con
     if ((rc = check_drop(p, seed, "smt_attn_bwd_dropout", &drop))) return rc;
     if (drop.t == 0)
         return smt_attn_bwd_kmask(q, k, v, o, d_o, lse, delta_ws, dq, dk, dv, key_mask, key_mask_ld, shape, stream);
-    return attn_bwd("smt_attn_bwd_dropout", q, k, v, o, d_o, lse, delta_ws, shape ? shape->S : 0, dq, dk, dv, key_mask,
+    return attn_bwd("smt_attn_bwd_dropout", q, k, v, o, d_o, lse, delta_ws, own_ld(shape), dq, dk, dv, key_mask,
                     key_mask_ld, drop, kNoDocs, shape, stream);
 }
 
@@ -1915,7 +1843,7 @@ int smt_attn_fwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const 
     DropArgs drop;
     int rc;
     if ((rc = check_drop(p, seed, fn, &drop))) return rc;
-    return attn_fwd(fn, q, k, v, o, lse, shape ? shape->S : 0, nullptr, 0, drop, DocArgs{doc_start, doc_end}, shape, stream);
+    return attn_fwd(fn, q, k, v, o, lse, own_ld(shape), nullptr, 0, drop, DocArgs{doc_start, doc_end}, shape, stream);
 }
 
 int smt_attn_bwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const smt_attn_tensor* v,
@@ -1930,7 +1858,7 @@ int smt_attn_bwd_docs(const smt_attn_tensor* q, const smt_attn_tensor* k, const 
     DropArgs drop;
     int rc;
     if ((rc = check_drop(p, seed, fn, &drop))) return rc;
-    return attn_bwd(fn, q, k, v, o, d_o, lse, delta_ws, shape ? shape->S : 0, dq, dk, dv, nullptr, 0, drop,
+    return attn_bwd(fn, q, k, v, o, d_o, lse, delta_ws, own_ld(shape), dq, dk, dv, nullptr, 0, drop,
                     DocArgs{doc_start, doc_end}, shape, stream);
 }
 

@@ -763,6 +763,11 @@ def _attn_tensor(t: torch.Tensor) -> _hip.AttnTensor:
     return _hip.AttnTensor(t.data_ptr(), sb, sh, ss)
 
 
+def _attn_ref(t: torch.Tensor):
+    """The tensor's descriptor as the C entry points take it (``const smt_attn_tensor*``)."""
+    return ctypes.byref(_attn_tensor(t))
+
+
 def _attn_ready(t: torch.Tensor) -> torch.Tensor:
     if t.stride(-1) == 1 and not any(s % 8 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0:
         return t
@@ -901,10 +906,21 @@ def flash_dropout_mask(B: int, Hq: int, S: int, p: float, seed, device) -> torch
     keep = torch.empty(B, Hq, S, S, dtype=torch.uint8, device=device)
     shape = _hip.AttnShape(B, Hq, Hq, S, 1.0, _hip.DTYPE_BF16)
     with torch.cuda.device(device):
-        rc = _hip.load().smt_attn_dropout_mask(keep.data_ptr(), float(p), seed_t.data_ptr() if t else None,
+        rc = _hip.load().smt_attn_dropout_mask(keep.data_ptr(), float(p), _hip._ptr(seed_t),
                                                ctypes.byref(shape), _stream(keep))
     _hip._check(rc, "smt_attn_dropout_mask")
     return keep.bool()
+
+
+def _key_mask_args(key_mask, B: int, S: int, device, prefix: str, noun: str):
+    """(pointer, row stride) of an optional :class:`KeyMask` over the S keys of B rows, as the C entry
+    points take them; ``prefix`` and ``noun`` word the caller's message."""
+    if key_mask is None:
+        return None, 0
+    if key_mask.S != S or key_mask.bits.shape[0] != B or key_mask.bits.device != device:
+        raise ValueError(f"{prefix}: key mask for [{key_mask.bits.shape[0]}, {key_mask.S}] keys, "
+                         f"{noun} has [{B}, {S}]")
+    return key_mask.bits.data_ptr(), key_mask.bits.shape[1]
 
 
 class FlashAttnFn(torch.autograd.Function):
@@ -937,14 +953,8 @@ class FlashAttnFn(torch.autograd.Function):
                 raise NotImplementedError("flash attention: per-head extent must stay below 2 GiB")
         o = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
         lse = torch.empty(B, Hq, (S + 3) & ~3, dtype=torch.float32, device=q.device)
-        ov = o.transpose(1, 2)
         shape = _hip.AttnShape(B, Hq, Hkv, S, float(scale), _dt(q))
-        km, km_ld = None, 0
-        if key_mask is not None:
-            if key_mask.S != S or key_mask.bits.shape[0] != B or key_mask.bits.device != q.device:
-                raise ValueError(f"flash attention: key mask for [{key_mask.bits.shape[0]}, {key_mask.S}] keys, "
-                                 f"batch has [{B}, {S}]")
-            km, km_ld = key_mask.bits.data_ptr(), key_mask.bits.shape[1]
+        km, km_ld = _key_mask_args(key_mask, B, S, q.device, "flash attention", "batch")
         ds = de = None
         if doc_mask is not None:
             ds, de = doc_mask.start, doc_mask.end
@@ -957,13 +967,9 @@ class FlashAttnFn(torch.autograd.Function):
         if dropout_p != 0.0 and dropout_threshold(dropout_p):
             seed_t = (torch.empty(1, dtype=torch.int64, device=q.device).random_() if seed is None
                       else _seed_tensor(seed, q.device))
-        rc = _hip.load().smt_attn_fwd_ld(ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)),
-                                         ctypes.byref(_attn_tensor(v)), ctypes.byref(_attn_tensor(ov)),
-                                         lse.data_ptr(), lse.shape[2], km, km_ld,
-                                         ds.data_ptr() if ds is not None else None,
-                                         de.data_ptr() if de is not None else None,
-                                         dropout_p if seed_t is not None else 0.0,
-                                         seed_t.data_ptr() if seed_t is not None else None,
+        T, P = _attn_ref, _hip._ptr
+        rc = _hip.load().smt_attn_fwd_ld(T(q), T(k), T(v), T(o.transpose(1, 2)), lse.data_ptr(), lse.shape[2], km, km_ld,
+                                         P(ds), P(de), dropout_p if seed_t is not None else 0.0, P(seed_t),
                                          ctypes.byref(shape), _stream(q))
         _hip._check(rc, "smt_attn_fwd_ld")
         ctx.save_for_backward(q, k, v, o, lse, key_mask.bits if key_mask is not None else None, seed_t, ds, de)
@@ -977,8 +983,7 @@ class FlashAttnFn(torch.autograd.Function):
         q, k, v, o, lse, km, seed_t, ds, de = ctx.saved_tensors
         B, Hq, S, D = q.shape
         Hkv = k.shape[1]
-        do = do if (do.stride(-1) == 1 and not any(s % 8 for s in do.stride()[:3]) and do.data_ptr() % 16 == 0) \
-            else do.contiguous()
+        do = _attn_ready(do)
         if ctx.joint:
             # one [B, S, (Hq + 2 Hkv) D] buffer holding [dq | dk | dv] row by row: q/k/v_proj's data
             # gradients then run as one GEMM (dgrad.py, the engine's joint transposed copy)
@@ -995,17 +1000,11 @@ class FlashAttnFn(torch.autograd.Function):
         if do.dtype != q.dtype:
             do = do.to(q.dtype)
         shape = _hip.AttnShape(B, Hq, Hkv, S, ctx.scale, _dt(q))
-        T = _attn_tensor
-        rc = _hip.load().smt_attn_bwd_ld(ctypes.byref(T(q)), ctypes.byref(T(k)), ctypes.byref(T(v)),
-                                         ctypes.byref(T(o.transpose(1, 2))), ctypes.byref(T(do.transpose(1, 2))),
-                                         lse.data_ptr(), delta.data_ptr(), lse.shape[2], ctypes.byref(T(dq)),
-                                         ctypes.byref(T(dk)), ctypes.byref(T(dv)),
-                                         km.data_ptr() if km is not None else None,
-                                         km.shape[1] if km is not None else 0,
-                                         ds.data_ptr() if ds is not None else None,
-                                         de.data_ptr() if de is not None else None,
-                                         ctx.dropout_p if seed_t is not None else 0.0,
-                                         seed_t.data_ptr() if seed_t is not None else None,
+        T, P = _attn_ref, _hip._ptr
+        rc = _hip.load().smt_attn_bwd_ld(T(q), T(k), T(v), T(o.transpose(1, 2)), T(do.transpose(1, 2)), lse.data_ptr(),
+                                         delta.data_ptr(), lse.shape[2], T(dq), T(dk), T(dv), P(km),
+                                         km.shape[1] if km is not None else 0, P(ds), P(de),
+                                         ctx.dropout_p if seed_t is not None else 0.0, P(seed_t),
                                          ctypes.byref(shape), _stream(q))
         _hip._check(rc, "smt_attn_bwd_ld")
         return dq, dk, dv, None, None, None, None, None, None, None
@@ -1109,12 +1108,7 @@ def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_of
     for t in (k, v):
         if Skv * t.stride(2) * 2 >= 2 ** 31:
             raise NotImplementedError("cached flash attention: per-head extent must stay below 2 GiB")
-    km, km_ld = None, 0
-    if key_mask is not None:
-        if key_mask.S != Skv or key_mask.bits.shape[0] != B or key_mask.bits.device != q.device:
-            raise ValueError(f"cached flash attention: key mask for [{key_mask.bits.shape[0]}, {key_mask.S}] keys, "
-                             f"cache has [{B}, {Skv}]")
-        km, km_ld = key_mask.bits.data_ptr(), key_mask.bits.shape[1]
+    km, km_ld = _key_mask_args(key_mask, B, Skv, q.device, "cached flash attention", "cache")
     o = torch.empty(B, Sq, Hq, D, dtype=q.dtype, device=q.device)
     lse = torch.empty(B, Hq, Sq, dtype=torch.float32, device=q.device) if return_lse else None
     shape = _hip.AttnShape(B, Hq, Hkv, Skv, float(scale if scale is not None else D ** -0.5), _dt(q))
@@ -1125,9 +1119,8 @@ def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_of
     ws_bytes = lib.smt_attn_cached_workspace(ctypes.byref(shape), Sq, num_splits)
     _hip._check(min(ws_bytes, 0), "smt_attn_cached_workspace")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes else None
-    tensors = (ctypes.byref(_attn_tensor(q)), ctypes.byref(_attn_tensor(k)), ctypes.byref(_attn_tensor(v)),
-               ctypes.byref(_attn_tensor(o.transpose(1, 2))), lse.data_ptr() if lse is not None else None, km, km_ld)
-    tail = (num_splits, ws.data_ptr() if ws is not None else None, ctypes.byref(shape), _stream(q))
+    tensors = (_attn_ref(q), _attn_ref(k), _attn_ref(v), _attn_ref(o.transpose(1, 2)), _hip._ptr(lse), km, km_ld)
+    tail = (num_splits, _hip._ptr(ws), ctypes.byref(shape), _stream(q))
     with torch.cuda.device(q.device):
         if pos is not None:
             rc = lib.smt_attn_fwd_cached_pos(*tensors, Sq, pos.data_ptr(), 0 if pos.numel() == 1 else 1, *tail)

@@ -13,16 +13,13 @@ import torch
 import torch.nn.functional as F
 
 from sparse_matrix_tuning_amd.fused_llama import FlashAttnFn, KeyMask, flash_attention, smt_flash_mask
+from tests.attn_ref import DEV, allowed_causal, inputs, ref32, rel as _rel
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 
 
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
+# _ref and _sdpa_bf16 stay here and not in tests/attn_ref.py: they are torch's own sdpa (fp32 and bf16),
+# the yardstick this file's header names, not the explicit-mask reference.
 def _ref(q, k, v, g, scale):
     G = q.shape[1] // k.shape[1]
     qf = q.detach().float().requires_grad_(True)
@@ -49,14 +46,8 @@ def _sdpa_bf16(q, k, v, g):
     (2, 8, 2, 256, "hf"), (1, 4, 4, 200, "hf"), (1, 8, 1, 384, "contig"), (2, 4, 2, 1024, "hf"), (1, 2, 2, 4, "hf"),
     (1, 40, 40, 512, "hf")])                                   # LLaMA-2-13B heads (config 4)
 def test_flash_attention_matches_fp32_reference(B, Hq, Hkv, S, layout):
-    torch.manual_seed(S + Hq)
     D = 128
-    if layout == "hf":      # [B, S, H, D] storage viewed as [B, H, S, D], as transformers hands them over
-        mk = lambda H: torch.randn(B, S, H, D, device=DEV).bfloat16().transpose(1, 2).requires_grad_(True)
-    else:
-        mk = lambda H: torch.randn(B, H, S, D, device=DEV).bfloat16().requires_grad_(True)
-    q, k, v = mk(Hq), mk(Hkv), mk(Hkv)
-    g = torch.randn(B, S, Hq, D, device=DEV).bfloat16()
+    q, k, v, g = inputs(B, Hq, Hkv, S, layout, torch.bfloat16, S + Hq)
     scale = D ** -0.5
     o = flash_attention(q, k, v)
     assert o.shape == (B, S, Hq, D) and o.dtype == torch.bfloat16
@@ -111,19 +102,7 @@ def test_flash_attention_rejects_unsupported():
 def _ref_masked(q, k, v, g, scale, keep):
     """fp32 reference with a key mask ``keep`` [B, S] (bool) AND causal; a row with no visible key
     has zero output and zero gradients (the kernels' safe-softmax convention)."""
-    G = q.shape[1] // k.shape[1]
-    qf, kf, vf = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-    S = q.shape[2]
-    causal = torch.ones(S, S, dtype=torch.bool, device=q.device).tril()
-    allowed = causal[None, None] & keep[:, None, None, :]
-    s = (qf @ kf.repeat_interleave(G, 1).transpose(-1, -2)) * scale
-    s = s.masked_fill(~allowed, float("-inf"))
-    any_key = allowed.any(-1, keepdim=True)
-    p = torch.softmax(s.masked_fill(~any_key, 0.0), -1) * any_key
-    o = p @ vf.repeat_interleave(G, 1)
-    o.transpose(1, 2).backward(g.float())
-    lse2 = torch.logsumexp(s, dim=-1) / math.log(2.0)
-    return o.transpose(1, 2).detach(), qf.grad, kf.grad, vf.grad, lse2, any_key.squeeze(-1)
+    return ref32(q, k, v, g, scale, allowed_causal(q.shape[2], keep))
 
 
 @pytest.mark.parametrize("B,Hq,Hkv,S", [(3, 8, 2, 256), (2, 4, 4, 200), (2, 32, 8, 1024)])
@@ -132,11 +111,8 @@ def test_flash_attention_key_mask_matches_fp32_reference(B, Hq, Hkv, S):
     sequence (LLaMA-3's pad id 0 is an ordinary token, deepspeed_helpers.py:600-602, and the collator's
     mask is input_ids != pad, helper.py:194-204), including a row whose first key is masked (its first
     queries see no key at all)."""
-    torch.manual_seed(S + B)
     D = 128
-    mk = lambda H: torch.randn(B, S, H, D, device=DEV).bfloat16().transpose(1, 2).requires_grad_(True)
-    q, k, v = mk(Hq), mk(Hkv), mk(Hkv)
-    g = torch.randn(B, S, Hq, D, device=DEV).bfloat16()
+    q, k, v, g = inputs(B, Hq, Hkv, S, "hf", torch.bfloat16, S + B)
     keep = torch.ones(B, S, dtype=torch.bool, device=DEV)
     keep[0, S - S // 3:] = False                       # right padding
     keep[1, S // 2 + 7:] = False

@@ -23,27 +23,15 @@ from sparse_matrix_tuning_amd import fused_llama as fl
 from sparse_matrix_tuning_amd.fused_llama import (DocMask, KeyMask, dropout_effective_p, flash_attention,
                                                   flash_dropout_mask, smt_flash_attention_forward, smt_flash_mask)
 from tests import test_gpu_attention as plain
-from tests import test_gpu_attention_dropout as dref
 from tests import test_gpu_attention_packed as pref
+from tests.attn_ref import D, DEV, allowed_causal, allowed_docs, eager16, inputs, ref32, rel as _rel
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-D = 128
 LENGTHS = [1, 3, 33, 66, 130, 259, 517]
 
 
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
 def _inputs(B, Hq, Hkv, S, layout="hf", dtype=torch.bfloat16, seed=0):
-    torch.manual_seed(seed + S + Hq)
-    if layout == "hf":      # [B, S, H, D] storage viewed as [B, H, S, D], as transformers hands them over
-        mk = lambda H: torch.randn(B, S, H, D, device=DEV).to(dtype).transpose(1, 2).requires_grad_(True)
-    else:
-        mk = lambda H: torch.randn(B, H, S, D, device=DEV).to(dtype).requires_grad_(True)
-    return mk(Hq), mk(Hkv), mk(Hkv), torch.randn(B, S, Hq, D, device=DEV).to(dtype)
+    return inputs(B, Hq, Hkv, S, layout, dtype, seed + S + Hq)
 
 
 def _run(q, k, v, g, **kw):
@@ -92,7 +80,7 @@ def test_any_length_key_mask(S):
     km = smt_flash_mask(B, S, S, attention_mask=keep.long())
     assert isinstance(km, KeyMask)
     o, lse, dq, dk, dv = _run(q, k, v, g, key_mask=km, any_length=True)
-    ro, rdq, rdk, rdv, rlse, visible = plain._ref_masked(q, k, v, g, D ** -0.5, keep)
+    ro, rdq, rdk, rdv, rlse, visible = ref32(q, k, v, g, D ** -0.5, allowed_causal(S, keep))
     for name, mine, ref in (("o", o, ro), ("dq", dq, rdq), ("dk", dk, rdk), ("dv", dv, rdv)):
         e = _rel(mine, ref)
         print(f"S {S} {name}: rel err {e:.3e}")
@@ -115,8 +103,8 @@ def test_any_length_dropout(S, p):
     o, lse, dq, dk, dv = _run(q, k, v, g, dropout_p=p, seed=seed, any_length=True)
     M = flash_dropout_mask(B, Hq, S, p, seed, DEV)
     r = 1.0 / (1.0 - dropout_effective_p(p))
-    ro, rdq, rdk, rdv, rlse, vis = dref._ref32(q, k, v, g, D ** -0.5, M, r, None)
-    eo, edq, edk, edv = dref._eager16(q, k, v, g, D ** -0.5, M, r, None)
+    ro, rdq, rdk, rdv, rlse, vis = ref32(q, k, v, g, D ** -0.5, allowed_causal(S), M, r)
+    eo, edq, edk, edv = eager16(q, k, v, g, D ** -0.5, allowed_causal(S), M, r)
     for name, mine, eager, ref in (("o", o, eo, ro), ("dq", dq, edq, rdq), ("dk", dk, edk, rdk), ("dv", dv, edv, rdv)):
         e, es = _rel(mine, ref), _rel(eager, ref)
         print(f"S {S} p {p} {name}: rel err {e:.3e} (16-bit eager {es:.3e})")
@@ -140,9 +128,9 @@ def test_any_length_documents(S, rows):
     dm = pref._doc_mask(rows, S)
     assert isinstance(dm, DocMask)
     o, lse, dq, dk, dv = _run(q, k, v, g, doc_mask=dm, any_length=True)
-    allowed = pref._allowed(rows, S)
-    ro, rdq, rdk, rdv, rlse = pref._ref32(q, k, v, g, D ** -0.5, allowed, None, 1.0)
-    eo, edq, edk, edv = pref._eager16(q, k, v, g, D ** -0.5, allowed, None, 1.0)
+    allowed = allowed_docs(rows, S)
+    ro, rdq, rdk, rdv, rlse, _ = ref32(q, k, v, g, D ** -0.5, allowed)
+    eo, edq, edk, edv = eager16(q, k, v, g, D ** -0.5, allowed)
     for name, mine, eager, ref in (("o", o, eo, ro), ("dq", dq, edq, rdq), ("dk", dk, edk, rdk), ("dv", dv, edv, rdv)):
         e, es = _rel(mine, ref), _rel(eager, ref)
         print(f"S {S} {name}: rel err {e:.3e} (16-bit eager {es:.3e})")
@@ -241,7 +229,7 @@ def test_interface_with_grad_at_an_odd_length():
     assert isinstance(km, KeyMask)
     o, _ = smt_flash_attention_forward(None, q, k, v, km)
     o.backward(g)
-    ro, rdq, rdk, rdv, _, _ = plain._ref_masked(q, k, v, g, D ** -0.5, keep)
+    ro, rdq, rdk, rdv, _, _ = ref32(q, k, v, g, D ** -0.5, allowed_causal(S, keep))
     for name, mine, ref in (("o", o, ro), ("dq", q.grad, rdq), ("dk", k.grad, rdk), ("dv", v.grad, rdv)):
         assert _rel(mine, ref) <= 8e-3, (name, _rel(mine, ref))
     # packed rows
@@ -249,9 +237,9 @@ def test_interface_with_grad_at_an_odd_length():
     rows = [[10, 27], [37]]
     o, _ = smt_flash_attention_forward(None, q, k, v, pref._doc_mask(rows, S))
     o.backward(g)
-    allowed = pref._allowed(rows, S)
-    ro, rdq, rdk, rdv, _ = pref._ref32(q, k, v, g, D ** -0.5, allowed, None, 1.0)
-    eo, edq, edk, edv = pref._eager16(q, k, v, g, D ** -0.5, allowed, None, 1.0)
+    allowed = allowed_docs(rows, S)
+    ro, rdq, rdk, rdv, _, _ = ref32(q, k, v, g, D ** -0.5, allowed)
+    eo, edq, edk, edv = eager16(q, k, v, g, D ** -0.5, allowed)
     for name, mine, eager, ref in (("o", o, eo, ro), ("dq", q.grad, edq, rdq), ("dk", k.grad, edk, rdk),
                                    ("dv", v.grad, edv, rdv)):
         e, es = _rel(mine, ref), _rel(eager, ref)
@@ -370,6 +358,6 @@ def test_smt_mini_llama_on_a_collated_batch_of_odd_length():
         x, g = seen_x[n].cpu(), seen_g[n].cpu()
         truth = ref.tile_grads_fp64(g, x, m.index_list)
         _gi, ref_gw = ref.linearz_backward(g, x, m.weight.detach().cpu(), m.index_list)
-        err, ref_err = plain._rel(m.selected_weight.grad.cpu(), truth), plain._rel(ref_gw, truth)
+        err, ref_err = _rel(m.selected_weight.grad.cpu(), truth), _rel(ref_gw, truth)
         print(f"{n}: tile grads vs fp64 {err:.2e} (reference {ref_err:.2e})")
         assert err <= max(1e-3, 1.1 * ref_err), (n, err, ref_err)

@@ -4,49 +4,34 @@ kernel against an fp32 masked softmax on the same 16-bit inputs. The bar is the 
 sdpa with the same boolean mask), lse (log2 units) within 2e-3 abs. Rows without a visible key:
 o == 0, lse == +inf. B = 2 throughout; the shapes are the smallest that reach each branch (one tile,
 a ragged tile, several tiles, several splits, empty splits, two column blocks)."""
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 from sparse_matrix_tuning_amd.fused_llama import (CacheMask, DocMask, KeyMask, flash_attention, flash_attention_cached,
                                                   smt_flash_attention_forward, smt_flash_mask)
+from tests.attn_ref import D, DEV, allowed_cached, ref32, rel as _rel
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-B, D = 2, 128
-
-
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
+B = 2
 
 
 def _allowed(Sq, Skv, q_offset, keep):
-    """bool [B, Sq, Skv]: query i (at position q_offset + i) sees key j."""
-    pos = q_offset + torch.arange(Sq, device=DEV)
-    a = (torch.arange(Skv, device=DEV)[None, :] <= pos[:, None])[None].expand(B, Sq, Skv)
-    return a & keep[:, None, :] if keep is not None else a
+    """bool [B, 1, Sq, Skv]: query i (at position q_offset + i) sees key j."""
+    return allowed_cached(B, Sq, Skv, q_offset, keep)
 
 
 def _ref_masked(q, k, v, scale, allowed):
-    """fp32 masked softmax; a row with no visible key has zero output (the kernels' convention).
-    Returns o [B, Sq, Hq, D], lse in log2 units [B, Hq, Sq], visible [B, 1, Sq]."""
-    G = q.shape[1] // k.shape[1]
-    qf, kf, vf = q.float(), k.float().repeat_interleave(G, 1), v.float().repeat_interleave(G, 1)
-    s = (qf @ kf.transpose(-1, -2)) * scale
-    s = s.masked_fill(~allowed[:, None], float("-inf"))
-    any_key = allowed.any(-1)[:, None, :, None]
-    p = torch.softmax(s.masked_fill(~any_key, 0.0), -1) * any_key
-    o = p @ vf
-    return o.transpose(1, 2), torch.logsumexp(s, dim=-1) / math.log(2.0), any_key.squeeze(-1)
+    """The fp32 reference, forward only: o [B, Sq, Hq, D], lse in log2 units and visible, both [B, Hq, Sq]."""
+    o, _, _, _, lse2, visible = ref32(q, k, v, None, scale, allowed)
+    return o, lse2, visible
 
 
+# torch's own 16-bit sdpa under the boolean mask (the bar of this file's header), so not in tests/attn_ref.py
 def _sdpa16(q, k, v, scale, allowed):
     G = q.shape[1] // k.shape[1]
     o = F.scaled_dot_product_attention(q, k.repeat_interleave(G, 1), v.repeat_interleave(G, 1),
-                                       attn_mask=allowed[:, None], scale=scale)
+                                       attn_mask=allowed, scale=scale)
     return o.transpose(1, 2)
 
 

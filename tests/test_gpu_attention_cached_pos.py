@@ -5,18 +5,15 @@ tile partition from the position it reads, exactly as the host does from q_offse
 independently, against an fp32 masked softmax with the project's bar (tests/test_gpu_attention_cached.py:
 relative norm error of o <= max(8e-3, 1.5 x torch's 16-bit sdpa), lse within 2e-3 abs). The graph
 replays and the sync-debug leg are the ones that show the host reads nothing. B = 2 or 3, head_dim 128."""
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 from sparse_matrix_tuning_amd.fused_llama import (CacheMask, KeyMask, flash_attention_cached, smt_flash_attention_forward,
                                                   smt_flash_mask)
+from tests.attn_ref import D, DEV, allowed_cached, ref32, rel as _rel
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-D = 128
 ENDS = (1, 63, 64, 65, 128, 129)                          # p + Sq: one tile, the ragged tile, the tile boundary
 SPLITS = (1, 2, 3, 7)                                     # 7 splits over 1-3 tiles: empty splits; 1: direct store
 
@@ -92,11 +89,6 @@ def test_one_position_per_batch_row(Sq):
     _same(flash_attention_cached(q, k, v, q_offset=pos.int(), num_splits=3, return_lse=True), ref, "int32 [B]")
 
 
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
 @pytest.mark.parametrize("splits", [1, 3])
 def test_key_mask_against_the_fp32_softmax(splits):
     """Independent of the host-offset call. Capacity 200, rows at 129 and 150, Sq 2: row 0 has a hole,
@@ -115,18 +107,14 @@ def test_key_mask_against_the_fp32_softmax(splits):
     o, lse = flash_attention_cached(q, k, v, key_mask=KeyMask.from_padding_mask(keep), q_offset=pos, num_splits=splits,
                                     return_lse=True)
     G, scale = Hq // Hkv, D ** -0.5
-    qpos = pos[:, None] + torch.arange(Sq, device=DEV)[None]                                # [B, Sq]
-    allowed = (torch.arange(cap, device=DEV)[None, None, :] <= qpos[:, :, None]) & keep[:, None, :]
+    allowed = allowed_cached(B, Sq, cap, pos, keep)                                         # [B, 1, Sq, cap]
     clean = lambda t: torch.where(keep[:, None, :, None], t, torch.zeros_like(t))
     kc, vc = clean(k), clean(v)
-    kf, vf = kc.float().repeat_interleave(G, 1), vc.float().repeat_interleave(G, 1)
-    s = ((q.float() @ kf.transpose(-1, -2)) * scale).masked_fill(~allowed[:, None], float("-inf"))
-    any_key = allowed.any(-1)[:, None, :, None]                                             # [B, 1, Sq, 1]
-    ro = ((torch.softmax(s.masked_fill(~any_key, 0.0), -1) * any_key) @ vf).transpose(1, 2)
-    rlse = torch.logsumexp(s, dim=-1) / math.log(2.0)
-    vis_o = any_key.squeeze(-1).transpose(1, 2)[..., None].expand(B, Sq, Hq, D)
+    ro, _, _, _, rlse, visible = ref32(q, kc, vc, None, scale, allowed)
+    vis_o = visible.transpose(1, 2)[..., None].expand(B, Sq, Hq, D)
+    # torch's own 16-bit sdpa under the same mask: the bar, so written here and not in tests/attn_ref.py
     so = F.scaled_dot_product_attention(q, kc.repeat_interleave(G, 1), vc.repeat_interleave(G, 1),
-                                        attn_mask=allowed[:, None], scale=scale).transpose(1, 2).float()
+                                        attn_mask=allowed, scale=scale).transpose(1, 2).float()
     so = so.masked_fill(~vis_o, 0.0)
     assert torch.isfinite(o.float()).all()
     assert (o[1].float() == 0).all() and torch.isinf(lse[1]).all() and (lse[1] > 0).all()

@@ -11,8 +11,6 @@ transformers' eager_attention_forward (scores in the dtype, fp32 softmax cast to
 M r, the PV matmul in the dtype) -- the bound of tests/test_gpu_attention.py with dropout on both
 sides. lse is that of the undropped probabilities: within 2e-3 (log2 units) of the undropped reference.
 """
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -20,16 +18,10 @@ import torch
 from sparse_matrix_tuning_amd import fused_llama as fl
 from sparse_matrix_tuning_amd.fused_llama import (KeyMask, dropout_effective_p, flash_attention, flash_dropout_mask,
                                                   smt_flash_mask)
+from tests.attn_ref import D, DEV, allowed_causal, eager16, inputs as _inputs, ref32, rel as _rel
 from tests.dropout_keep_ref import keep_mask
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-D = 128
-
-
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
 
 
 @pytest.mark.parametrize("B,H,S", [(2, 4, 200), (1, 8, 512)])
@@ -47,49 +39,6 @@ def test_exported_mask_is_the_documented_function(B, H, S, p, seed):
 def test_exported_mask_without_dropout_keeps_everything():
     assert flash_dropout_mask(1, 2, 64, 0.0, None, DEV).all()
     assert flash_dropout_mask(1, 2, 64, 0.001, 7, DEV).all()             # t == 0
-
-
-def _allowed(S, keep):
-    causal = torch.ones(S, S, dtype=torch.bool, device=DEV).tril()[None, None]
-    return causal if keep is None else causal & keep[:, None, None, :]
-
-
-def _ref32(q, k, v, g, scale, M, r, keep):
-    """fp32 reference with the mask M [B, Hq, S, S]; rows with no visible key: zero output / gradients."""
-    G = q.shape[1] // k.shape[1]
-    qf, kf, vf = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-    allowed = _allowed(q.shape[2], keep)
-    s = (qf @ kf.repeat_interleave(G, 1).transpose(-1, -2)) * scale
-    s = s.masked_fill(~allowed, float("-inf"))
-    any_key = allowed.any(-1, keepdim=True)
-    p = torch.softmax(s.masked_fill(~any_key, 0.0), -1) * any_key
-    o = (p * (M.float() * r)) @ vf.repeat_interleave(G, 1)
-    o.transpose(1, 2).backward(g.float())
-    lse2 = torch.logsumexp(s.detach(), dim=-1) / math.log(2.0)
-    return o.transpose(1, 2).detach(), qf.grad, kf.grad, vf.grad, lse2, any_key.squeeze(-1).expand_as(lse2)
-
-
-def _eager16(q, k, v, g, scale, M, r, keep):
-    """16-bit eager attention with the same mask, in transformers' eager_attention_forward order."""
-    G = q.shape[1] // k.shape[1]
-    qs, ks, vs = (t.detach().clone().requires_grad_(True) for t in (q, k, v))
-    allowed = _allowed(q.shape[2], keep)
-    s = (qs @ ks.repeat_interleave(G, 1).transpose(-1, -2)) * scale
-    s = s.masked_fill(~allowed, float("-inf"))
-    any_key = allowed.any(-1, keepdim=True)
-    p = (torch.softmax(s.masked_fill(~any_key, 0.0), -1, dtype=torch.float32) * any_key).to(q.dtype)
-    o = (p * (M.to(q.dtype) * r)) @ vs.repeat_interleave(G, 1)
-    o.transpose(1, 2).backward(g)
-    return o.transpose(1, 2).detach(), qs.grad, ks.grad, vs.grad
-
-
-def _inputs(B, Hq, Hkv, S, layout, dtype, seed):
-    torch.manual_seed(seed)
-    if layout == "hf":      # [B, S, H, D] storage viewed as [B, H, S, D], as transformers hands them over
-        mk = lambda H: torch.randn(B, S, H, D, device=DEV).to(dtype).transpose(1, 2).requires_grad_(True)
-    else:
-        mk = lambda H: torch.randn(B, H, S, D, device=DEV).to(dtype).requires_grad_(True)
-    return mk(Hq), mk(Hkv), mk(Hkv), torch.randn(B, S, Hq, D, device=DEV).to(dtype)
 
 
 def _key_mask(B, S):
@@ -128,8 +77,9 @@ def test_dropout_matches_fp32_reference_with_the_exported_mask(B, Hq, Hkv, S, p,
     o.backward(g)
     M = flash_dropout_mask(B, Hq, S, p, seed, DEV)
     r = 1.0 / (1.0 - dropout_effective_p(p))
-    ro, rdq, rdk, rdv, rlse, vis = _ref32(q, k, v, g, scale, M, r, keep)
-    eo, edq, edk, edv = _eager16(q, k, v, g, scale, M, r, keep)
+    allowed = allowed_causal(S, keep)
+    ro, rdq, rdk, rdv, rlse, vis = ref32(q, k, v, g, scale, allowed, M, r)
+    eo, edq, edk, edv = eager16(q, k, v, g, scale, allowed, M, r)
     for name, mine, eager, ref in (("o", o, eo, ro), ("dq", q.grad, edq, rdq), ("dk", k.grad, edk, rdk),
                                    ("dv", v.grad, edv, rdv)):
         e, es = _rel(mine, ref), _rel(eager, ref)
@@ -143,7 +93,7 @@ def test_dropout_matches_fp32_reference_with_the_exported_mask(B, Hq, Hkv, S, p,
         dead = ~keep[:, None, :, None].expand(B, Hkv, S, D)
         assert (k.grad.float()[dead] == 0).all() and (v.grad.float()[dead] == 0).all()
     # a row all of whose visible keys were dropped: o = 0 exactly, a finite lse, a zero dq row
-    gone = vis & ~(M & _allowed(S, keep)).any(-1)                       # [B, Hq, S]
+    gone = vis & ~(M & allowed).any(-1)                       # [B, Hq, S]
     if (S, p) == (200, 0.5):
         assert gone[:, :, 0].any() and not gone[:, :, 0].all()          # q = 0 sees key 0 only: dropped for some heads
     assert torch.isfinite(lse[gone]).all()

@@ -14,26 +14,18 @@ C ABI include/smt_attention.h ``smt_attn_*_docs``.
    patch_llama and smt_flash_mask: loss and input-embedding gradient against transformers' eager
    attention on the same packed input and against the three documents run on their own.
 """
-import math
-
 import pytest
 import torch
 
 from sparse_matrix_tuning_amd import fused_llama as fl
 from sparse_matrix_tuning_amd.fused_llama import (DocMask, dropout_effective_p, flash_attention, flash_dropout_mask)
+from tests.attn_ref import D, DEV, allowed_docs as _allowed, eager16, inputs, ref32, rel as _rel
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-D = 128
 
 DOCS_576 = [[1, 63, 64, 130, 62, 256],      # a length-1 document; boundaries on and off the 64 / 128 tile edges; ends at S
             [300, 276],                     # a boundary inside a 256-key block; a document longer than a block
             [576]]                          # no packing
-
-
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
 
 
 def _cu(lens):
@@ -47,51 +39,8 @@ def _doc_mask(rows, S):
     return DocMask.from_cu_seqlens([torch.tensor(_cu(r), device=DEV) for r in rows], len(rows), S)
 
 
-def _allowed(rows, S):
-    """The block-diagonal causal mask [B, 1, S, S], written out from the document lengths."""
-    m = torch.zeros(len(rows), 1, S, S, dtype=torch.bool)
-    for b, lens in enumerate(rows):
-        assert sum(lens) == S
-        at = 0
-        for n in lens:
-            m[b, 0, at:at + n, at:at + n] = torch.ones(n, n, dtype=torch.bool).tril()
-            at += n
-    return m.to(DEV)
-
-
-def _ref32(q, k, v, g, scale, allowed, M, r):
-    G = q.shape[1] // k.shape[1]
-    qf, kf, vf = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-    s = (qf @ kf.repeat_interleave(G, 1).transpose(-1, -2)) * scale
-    s = s.masked_fill(~allowed, float("-inf"))
-    p = torch.softmax(s, -1)
-    if M is not None:
-        p = p * (M.float() * r)
-    o = p @ vf.repeat_interleave(G, 1)
-    o.transpose(1, 2).backward(g.float())
-    lse2 = torch.logsumexp(s.detach(), dim=-1) / math.log(2.0)
-    return o.transpose(1, 2).detach(), qf.grad, kf.grad, vf.grad, lse2
-
-
-def _eager16(q, k, v, g, scale, allowed, M, r):
-    """16-bit eager attention with the same mask, in transformers' eager_attention_forward order."""
-    G = q.shape[1] // k.shape[1]
-    qs, ks, vs = (t.detach().clone().requires_grad_(True) for t in (q, k, v))
-    s = (qs @ ks.repeat_interleave(G, 1).transpose(-1, -2)) * scale
-    s = s.masked_fill(~allowed, float("-inf"))
-    p = torch.softmax(s, -1, dtype=torch.float32).to(q.dtype)
-    if M is not None:
-        p = p * (M.to(q.dtype) * r)
-    o = p @ vs.repeat_interleave(G, 1)
-    o.transpose(1, 2).backward(g)
-    return o.transpose(1, 2).detach(), qs.grad, ks.grad, vs.grad
-
-
 def _inputs(B, Hq, Hkv, S, dtype, seed):
-    """[B, S, H, D] storage viewed as [B, H, S, D], as transformers hands them over."""
-    torch.manual_seed(seed)
-    mk = lambda H: torch.randn(B, S, H, D, device=DEV).to(dtype).transpose(1, 2).requires_grad_(True)
-    return mk(Hq), mk(Hkv), mk(Hkv), torch.randn(B, S, Hq, D, device=DEV).to(dtype)
+    return inputs(B, Hq, Hkv, S, "hf", dtype, seed)
 
 
 CASES = [
@@ -119,8 +68,8 @@ def test_packed_rows_match_fp32_reference(Hq, Hkv, S, rows, dtype, joint, p):
     allowed = _allowed(rows, S)
     M = flash_dropout_mask(B, Hq, S, p, seed, DEV) if p else None
     r = 1.0 / (1.0 - dropout_effective_p(p)) if p else 1.0
-    ro, rdq, rdk, rdv, rlse = _ref32(q, k, v, g, scale, allowed, M, r)
-    eo, edq, edk, edv = _eager16(q, k, v, g, scale, allowed, M, r)
+    ro, rdq, rdk, rdv, rlse, _ = ref32(q, k, v, g, scale, allowed, M, r)
+    eo, edq, edk, edv = eager16(q, k, v, g, scale, allowed, M, r)
     for name, mine, eager, ref in (("o", o, eo, ro), ("dq", q.grad, edq, rdq), ("dk", k.grad, edk, rdk),
                                    ("dv", v.grad, edv, rdv)):
         e, es = _rel(mine, ref), _rel(eager, ref)
