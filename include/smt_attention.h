@@ -242,6 +242,58 @@ int     smt_attn_fwd_cached_pos(const smt_attn_tensor* q, const smt_attn_tensor*
                                 int32_t Sq, const int64_t* positions, int32_t positions_stride, int32_t num_splits,
                                 void* workspace, const smt_attn_shape* shape, hipStream_t stream);
 
+/*
+ * Beam-shared cache (additive entry points; the ABI version is unchanged; forward only): one decode
+ * position of beam search against a cache that is never reordered and never concatenated. shape->B = N
+ * samples (shape->S is not used), nb beams each; row r = n * nb + beam.
+ *   q, o               [N * nb][Hq][1][128]: smt_attn_tensor with sb the row stride (ss is not used)
+ *   lse                fp32 [N * nb][Hq] in the log2 units above, or NULL
+ *   k_prompt, v_prompt [N][Hkv][P_cap][128]: the prompt's keys, ONE copy per sample (the beams of a
+ *                      sample hold identical prompt rows); P <= P_cap of them are valid. With P == 0
+ *                      the two tensors are never touched and their ptr may be null.
+ *   prompt_mask        uint64 [N][prompt_mask_ld] over the prompt keys (bit as in smt_attn_fwd_kmask),
+ *                      prompt_mask_ld >= ceil(P / 64), or NULL; bits at j >= P are ignored
+ *   k_gen, v_gen       [N * nb][Hkv][T_cap][128]: physical slot s of sample n is row n * nb + s, and
+ *                      the key a slot wrote at step j is its row j; T <= T_cap steps are valid
+ *   anc                uint8 [N * nb][anc_ld], anc_ld >= T: anc[r][j] is the physical slot (0..nb-1)
+ *                      that holds the step-j key of row r's hypothesis
+ * Row r of sample n sees prompt key j < P iff its mask bit is set, and generated entry (slot s, step
+ * j < T) iff anc[r][j] == s; the result is the softmax over that set: smt_attn_fwd_cached with Sq = 1
+ * on the row's gathered cache, up to the order of summation. Generated entries have no mask of their
+ * own. A row with no visible key gets o = 0 and lse = +inf.
+ *
+ * The 32 columns of the kernel's products are (beam, query head of one KV head) pairs of one (sample,
+ * KV head), col = beam * G + g; nb * G > 32 takes further column blocks (correct for any nb, fast for
+ * nb * G <= 32). The tile list of a (sample, KV head) is the prompt's 64-key tiles, then every slot's
+ * generated tiles: each physical K / V row is fetched once per sample, not once per beam, and nothing
+ * is gathered. Rows at j >= P of the prompt buffers and j >= T of the generated buffers are never
+ * read, whatever they hold; a row that no column of a block sees (a dead hypothesis, a masked key)
+ * does not reach o, whatever it holds, an Inf or NaN included. num_splits, workspace: as in
+ * smt_attn_fwd_cached, over contiguous ranges of that tile list (fp32 partials, combined in split
+ * order, no atomics, bit-reproducible for a given num_splits; 1 writes o directly; 0 takes
+ * smt_attn_beams_splits(shape, nb, P, T), a pure host function, >= 1). smt_attn_beams_workspace: the
+ * bytes of `workspace` (16-byte aligned device memory) for num_splits (0 = the default); 0 when none
+ * is needed. Both return -1 for a bad shape, nb < 1, P < 0, T < 1 or num_splits < 0.
+ *
+ * The kernel is memory-safe for any contents of anc: a value only ever enters the comparison
+ * anc[r][j] == s against the slot counter s of the tile being swept (it masks a score or zeroes a V
+ * row in LDS); no address depends on it, and a value >= nb matches no slot (that key is then invisible to row r). The bytes read are rows
+ * [n * nb, n * nb + nb) x [0, T) of anc, nothing else.
+ *
+ * Returns -1 before any HIP call for a null shape / tensor / anc, nb < 1, P < 0, T < 1 (the current
+ * token's key is already in the cache), P > P_cap, T > T_cap, anc_ld < T, prompt_mask_ld <
+ * ceil(P / 64), Hq % Hkv != 0, a dtype that is not a 16-bit format, num_splits < 0 and a null
+ * workspace when one is needed; -2 for misaligned rows, and when the P rows (T rows) of one head of
+ * the prompt (generated) buffers, rounded up to whole tiles, span 2 GiB or more.
+ */
+int     smt_attn_beams_splits(const smt_attn_shape* shape /* B = N */, int32_t nb, int32_t P, int32_t T);
+int64_t smt_attn_beams_workspace(const smt_attn_shape* shape, int32_t nb, int32_t P, int32_t T, int32_t num_splits);
+int     smt_attn_fwd_beams(const smt_attn_tensor* q, const smt_attn_tensor* k_prompt, const smt_attn_tensor* v_prompt,
+                           const smt_attn_tensor* k_gen, const smt_attn_tensor* v_gen, const smt_attn_tensor* o,
+                           float* lse, const uint64_t* prompt_mask, int64_t prompt_mask_ld, const uint8_t* anc,
+                           int64_t anc_ld, int32_t nb, int32_t P, int32_t P_cap, int32_t T, int32_t T_cap,
+                           int32_t num_splits, void* workspace, const smt_attn_shape* shape, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

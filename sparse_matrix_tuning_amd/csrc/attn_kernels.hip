@@ -3,7 +3,8 @@
 // kernels (DROP instances, smt_attn_*_dropout), optional document mask of packed rows (DOC instances,
 // smt_attn_*_docs); and the forward-only split-KV kernel of calls against a KV cache (attn_decode_kernel,
 // smt_attn_fwd_cached; smt_attn_fwd_cached_pos with the query position read on the device, for a
-// pre-allocated cache). Any sequence length S >= 1, forward and backward: lse and delta are
+// pre-allocated cache; attn_beams_kernel, smt_attn_fwd_beams, one decode position of beam search against
+// a beam-shared cache that is never reordered). Any sequence length S >= 1, forward and backward: lse and delta are
 // [B][Hq][lse_ld] with a row stride lse_ld % 4 == 0 of their own (smt_attn_fwd_ld / smt_attn_bwd_ld),
 // which is all the 16-byte lse / delta fetch of the dK/dV kernel needs; the other entry points are
 // these with lse_ld = S.
@@ -1483,7 +1484,8 @@ void attn_decode_kernel(Args a) {
 }
 
 // One workgroup per (column, b*Hkv), one thread per d: the splits' partials in split order.
-template <int F>
+// ROWS (smt_attn_fwd_beams, where the "query position" qi is the beam): lse is [B * Sq][Hq], row b * Sq + qi.
+template <int F, bool ROWS = false>
 __global__ __launch_bounds__(kD)
 void attn_decode_combine_kernel(DecArgs a) {
     const int col = blockIdx.x, bh = blockIdx.y, d = threadIdx.x;
@@ -1505,7 +1507,254 @@ void attn_decode_combine_kernel(DecArgs a) {
     const bool any = L > 0.f;
     const uint32_t r = pk16<F>(any ? acc / L : 0.f, 0.f);
     a.o[b * a.o_sb + h * a.o_sh + (int64_t)qi * a.o_ss + d] = (uint16_t)(r & 0xffffu);
-    if (a.lse && d == 0) a.lse[((int64_t)b * a.Hq + h) * a.Sq + qi] = any ? M + __log2f(L) : __builtin_huge_valf();
+    if (a.lse && d == 0)
+        a.lse[ROWS ? ((int64_t)b * a.Sq + qi) * a.Hq + h : ((int64_t)b * a.Hq + h) * a.Sq + qi] =
+            any ? M + __log2f(L) : __builtin_huge_valf();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Beam-shared cache, smt_attn_fwd_beams: one query position of N samples x nb beams against a cache
+// that is never reordered. The prompt's K / V is stored once per sample; the generated K / V of step
+// j sits in row j of the physical slot that wrote it, and anc[row][j] names the slot that holds the
+// step-j key of that row's hypothesis. The 32 columns of a workgroup are (beam, head within the KV
+// group) pairs of ONE (sample, KV head), col = beam * G + g, so the beam plays the part the query
+// position plays in attn_decode_kernel and the ring, the lane maps, the partials and the combine are
+// that kernel's. The tile list of a workgroup's (sample, KV head) is the prompt's 64-key tiles, then
+// every slot's generated tiles, slot by slot: each physical row is fetched once per sample, whatever
+// the number of beams that see it, and nothing is gathered. Splits are contiguous ranges of that list.
+// Visibility is one 64-bit word per (column, tile): the prompt mask word for a prompt tile; for a
+// generated tile of slot s, bit j = (anc[row][64 g + j] == s), built with one byte load per beam of
+// the block (lane = the tile's row) and a ballot. The bytes of the next tile are fetched before its
+// K / V (the loop's own wait covers them). anc only ever enters that comparison: no address depends
+// on a value in it, and a value >= nb matches no slot. Rows past P (prompt) and past T (generated)
+// are outside the buffer descriptors; a row inside them that no column of the block sees (a dead
+// hypothesis, a masked prompt key) has its V row zeroed in LDS, and its scores leave by selection.
+// ------------------------------------------------------------------------------------------------
+struct BeamArgs : DecArgs {                // DecArgs: q / o with sb = nb rows, ss = one row; k, v = the prompt; Sq = nb
+    Tns kg, vg;                            // generated K / V: row n * nb + slot, head, step
+    const uint8_t* anc;
+    int64_t anc_ld;
+    int nb, P, T, pt, gt;                  // pt / gt: 64-key tiles of the prompt / of one slot's generated rows
+};
+
+struct BeamTile {
+    int s, g;                              // s: the slot, -1 = the prompt; g: the tile within that segment
+};
+__device__ __forceinline__ BeamTile beam_tile(int t, int pt, int gt) {
+    if (t < pt) return BeamTile{-1, t};
+    const int u = t - pt, s = u / gt;
+    return BeamTile{s, u - s * gt};
+}
+__device__ __forceinline__ BeamTile beam_next(BeamTile c, int pt, int gt) {
+    ++c.g;
+    if (c.g == (c.s < 0 ? pt : gt)) {
+        c.g = 0;
+        ++c.s;
+    }
+    return c;
+}
+// the first `rem` bits set (rem >= 64: all, rem <= 0: none)
+__device__ __forceinline__ uint64_t low_bits(int rem) { return rem >= 64 ? ~0ull : (rem <= 0 ? 0ull : (1ull << rem) - 1ull); }
+
+constexpr int kBeamPre = 8;                // beams of a column block whose ancestry bytes are fetched a tile ahead
+
+template <bool KMASK, int F, bool DIRECT>
+__global__ __launch_bounds__(64)
+void attn_beams_kernel(BeamArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // K/V ring: 2 x 32 KiB
+    const int cb = blockIdx.x, sp = blockIdx.y, bh = blockIdx.z;
+    const int n = bh / a.Hkv, hk = bh - n * a.Hkv;
+    const int lane = threadIdx.x, hi = lane >> 5, l32 = lane & 31;
+    const int col = cb * kDecCols + l32;
+    const bool cvalid = col < a.ncols;
+    const int beam = cvalid ? col / a.G : -1;                  // an unused column sees no key
+    const int h = hk * a.G + (cvalid ? col - beam * a.G : 0);
+    // the beams this column block holds (workgroup-uniform)
+    const int b_lo = (cb * kDecCols) / a.G, b_hi = min(a.nb - 1, (cb * kDecCols + kDecCols - 1) / a.G);
+    const int t0 = sp * a.tps, t1 = min(a.pt + a.nb * a.gt, t0 + a.tps);
+    const int64_t nslots = (int64_t)gridDim.z * a.ncb * a.nsplit;
+    const int64_t slot = ((int64_t)bh * a.ncb + cb) * a.nsplit + sp;
+    if (t0 >= t1) {                                            // an empty split (never with DIRECT)
+        if (!DIRECT && cvalid && hi == 0) {
+            float* ml = dec_ws_ml(a, nslots, slot, l32);
+            ml[0] = kNegInf;
+            ml[1] = 0.f;
+        }
+        return;
+    }
+    const int64_t row0 = (int64_t)n * a.nb;                    // the sample's first row / slot
+    const uint64_t* km = KMASK ? a.kmask + (int64_t)n * a.kmask_ld : nullptr;
+    bf16x8_t qf[8];
+    {
+        const uint16_t* qp = a.q.p + n * a.q.sb + h * a.q.sh + (int64_t)(cvalid ? beam : 0) * a.q.ss;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            if (cvalid) qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + 16 * ks + 8 * hi);
+            else qf[ks] = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
+        }
+    }
+    const uint32_t lds0 = lds_addr(lds);
+    const TrLane tl = tr_lane(lane);
+    f32x16_t o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[dt][i] = 0.f;
+    float m_run = kNegInf, l_run = 0.f;
+
+    // K, V of tile bt into slot t & 1. The descriptors end with the segment's last row (P - 1 of the
+    // prompt, T - 1 of a slot): later rows are never read (they land as zeros). The slot index comes
+    // from the tile counter, never from anc.
+    auto issue = [&](int t, BeamTile bt) {
+        const uint32_t s = lds0 + (uint32_t)((t & 1) * 2 * kTileB);
+        const bool pr = bt.s < 0;
+        const uint16_t* kb = pr ? a.k.p + n * a.k.sb + hk * a.k.sh : a.kg.p + (row0 + bt.s) * a.kg.sb + hk * a.kg.sh;
+        const uint16_t* vb = pr ? a.v.p + n * a.v.sb + hk * a.v.sh : a.vg.p + (row0 + bt.s) * a.vg.sb + hk * a.vg.sh;
+        const int64_t kss = pr ? a.k.ss : a.kg.ss, vss = pr ? a.v.ss : a.vg.ss;
+        const int rows = pr ? a.P : a.T;
+        const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(kb, (int64_t)(rows - 1) * kss * 2 + kRowB);
+        const __amdgpu_buffer_rsrc_t rv = uniform_rsrc(vb, (int64_t)(rows - 1) * vss * 2 + kRowB);
+        dma_rows(rk, kss, s, bt.g * kKV, bt.g * kKV, kKV / 4, lane);
+        dma_rows(rv, vss, s + kTileB, bt.g * kKV, bt.g * kKV, kKV / 4, lane);
+    };
+    // anc[row of beam b_lo + kBeamPre * chunk + i][64 g + lane] of a generated tile, -1 where there is
+    // no such beam, no such step (>= T) or the tile is the prompt's: -1 equals no slot
+    auto load_anc = [&](BeamTile bt, int chunk, int (&v)[kBeamPre]) {
+        const int j = bt.g * kKV + lane;
+#pragma unroll
+        for (int i = 0; i < kBeamPre; ++i) {
+            const int bm = b_lo + chunk * kBeamPre + i;
+            v[i] = (bt.s >= 0 && bm <= b_hi && j < a.T) ? (int)a.anc[(row0 + bm) * a.anc_ld + j] : -1;
+        }
+    };
+
+    BeamTile cur = beam_tile(t0, a.pt, a.gt);
+    int pre[kBeamPre];
+    load_anc(cur, 0, pre);
+    issue(t0, cur);
+    vm_wait_all();
+    vm_wait_all_known();                                       // the Q fragments and pre too (compiler-visible)
+    __syncthreads();
+    for (int t = t0; t < t1; ++t) {
+        // w_col: the keys of this tile this lane's column sees; w_any: the rows whose V stays (seen by a
+        // column of the block, or outside the descriptor and zero already)
+        uint64_t w_col, w_any;
+        if (cur.s < 0) {
+            const uint64_t in = low_bits(a.P - cur.g * kKV);
+            const uint64_t w = (KMASK ? km[cur.g] : ~0ull) & in;   // workgroup-uniform
+            w_col = cvalid ? w : 0ull;
+            w_any = w | ~in;
+        } else {
+            w_col = 0ull;
+            w_any = ~low_bits(a.T - cur.g * kKV);
+            for (int c = 0; b_lo + c * kBeamPre <= b_hi; ++c) {
+                if (c) load_anc(cur, c, pre);                  // more than kBeamPre beams in the block: fetched here
+#pragma unroll
+                for (int i = 0; i < kBeamPre; ++i) {
+                    const uint64_t w = __builtin_amdgcn_ballot_w64(pre[i] == cur.s);
+                    w_any |= w;
+                    if (beam == b_lo + c * kBeamPre + i) w_col = w;
+                }
+            }
+        }
+        const BeamTile nxt = beam_next(cur, a.pt, a.gt);
+        if (t + 1 < t1) {
+            load_anc(nxt, 0, pre);
+            issue(t + 1, nxt);
+        }
+        uint8_t* K = lds + (t & 1) * 2 * kTileB;
+        uint8_t* V = K + kTileB;
+        if (~w_any != 0ull) {
+            if (!key_bit(w_any, lane)) {                       // lane = the tile's row: a row no column sees
+#pragma unroll
+                for (int c = 0; c < 16; ++c) *reinterpret_cast<u32x4_t*>(V + lane * kRowB + 16 * c) = u32x4_t{0u, 0u, 0u, 0u};
+            }
+            __syncthreads();
+        }
+        f32x16_t sc[2];
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                sc[j] = mfma<F>(row_frag(K, 32 * j + l32, 32 * ks + 16 * hi), qf[ks], ks ? sc[j] : f32x16_t{});
+        float x[32];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) x[16 * j + i] = sc[j][i];
+        // hidden keys leave by selection
+        const uint64_t w_hi = w_col >> (4 * hi);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const int key = 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2);       // + 4 * hi, shifted in above
+            if (!key_bit(w_hi, key)) x[i] = kNegInf;
+        }
+        float mx = x[0];
+#pragma unroll
+        for (int i = 1; i < 32; ++i) mx = fmaxf(mx, x[i]);
+        const float m_tile = other_half_max(mx) * a.sl2;
+        const bool move = m_tile > m_run + kFwdThr;
+        const float m_new = move ? m_tile : m_run;
+        const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.f;
+        const float m_use = (m_new == kNegInf) ? 0.f : m_new;
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[i], a.sl2, -m_use));
+            sum += x[i];
+        }
+        l_run = l_run * alpha + sum;
+        m_run = m_new;
+        if (__builtin_amdgcn_ballot_w64(move) != 0) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
+        }
+        bf16x8_t pf[4];
+        pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[0]), pf[0], pf[1]);
+        pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[16]), pf[2], pf[3]);
+#pragma unroll
+        for (int nn = 0; nn < 16; ++nn)
+            o[nn >> 2] = mfma<F>(tr_frag(V, tl, 16 * (nn & 3), 32 * (nn >> 2)), pf[nn & 3], o[nn >> 2]);
+        vm_wait_all();
+        vm_wait_all_known();                                   // pre of the next tile has landed (compiler-visible)
+        __syncthreads();
+        cur = nxt;
+    }
+    const float l_tot = halves_sum(l_run);
+    if (!cvalid) return;
+    if (DIRECT) {
+        const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+        uint16_t* op = a.o + n * a.o_sb + h * a.o_sh + (int64_t)beam * a.o_ss;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                uint2 wd;
+                wd.x = pk16<F>(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv);
+                wd.y = pk16<F>(o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
+                *reinterpret_cast<uint2*>(op + 32 * dt + 8 * g + 4 * hi) = wd;
+            }
+        if (a.lse && hi == 0)
+            a.lse[(row0 + beam) * a.Hq + h] = l_tot > 0.f ? m_run + __log2f(l_tot) : __builtin_huge_valf();
+    } else {
+        const bool any = l_tot > 0.f;
+        if (any) {
+            float* po = dec_ws_o(a, slot, l32);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(po + 32 * dt + 8 * g + 4 * hi) =
+                        float4{o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
+        }
+        if (hi == 0) {
+            float* ml = dec_ws_ml(a, nslots, slot, l32);
+            ml[0] = any ? m_run : kNegInf;
+            ml[1] = any ? l_tot : 0.f;
+        }
+    }
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -1772,6 +2021,94 @@ int attn_fwd_cached(const char* fn, const smt_attn_tensor* q, const smt_attn_ten
     return check_launch("attn_decode_combine_kernel");
 }
 
+// Beam-shared cache: the shape (S is not used), the beam count and the fill levels. Host arithmetic only.
+int check_beams(const char* fn, const smt_attn_shape* s, int32_t nb, int32_t P, int32_t T) {
+    if (!s) return fail(-1, "%s: null shape", fn);
+    if (s->B <= 0 || s->Hq <= 0 || s->Hkv <= 0 || s->Hq % s->Hkv)
+        return fail(-1, "%s: bad shape B=%d Hq=%d Hkv=%d (Hq %% Hkv must be 0)", fn, s->B, s->Hq, s->Hkv);
+    if (!(s->scale > 0.f)) return fail(-1, "%s: scale must be > 0", fn);
+    if (s->dtype != SMT_DTYPE_BF16 && s->dtype != SMT_DTYPE_FP16)
+        return fail(-1, "%s: dtype %d is not a 16-bit format (SMT_DTYPE_BF16 / SMT_DTYPE_FP16)", fn, (int)s->dtype);
+    if (nb < 1) return fail(-1, "%s: nb = %d (at least one beam)", fn, (int)nb);
+    if (P < 0) return fail(-1, "%s: P = %d is negative", fn, (int)P);
+    if (T < 1) return fail(-1, "%s: T = %d (the current token's key is already in the cache)", fn, (int)T);
+    if ((int64_t)nb * (s->Hq / s->Hkv) > 0x7fffffffLL / 2 || (int64_t)s->B * s->Hkv > 65535 ||
+        (int64_t)s->B * nb > 0x7fffffffLL)
+        return fail(-1, "%s: B * Hkv must stay within 65535, nb * G below 2^30 and B * nb below 2^31", fn);
+    if ((int64_t)P / kKV + (int64_t)nb * ((int64_t)T / kKV + 1) > 0x3fffffffLL)
+        return fail(-1, "%s: P = %d, nb = %d, T = %d make more than 2^30 tiles", fn, (int)P, (int)nb, (int)T);
+    return 0;
+}
+int beam_col_blocks(const smt_attn_shape* s, int32_t nb) { return dec_col_blocks(s, nb); }
+int beam_tiles(int32_t nb, int32_t P, int32_t T) { return (P + kKV - 1) / kKV + nb * ((T + kKV - 1) / kKV); }
+// as dec_default_splits, over the tile list of one (sample, KV head)
+int beam_default_splits(const smt_attn_shape* s, int32_t nb, int32_t P, int32_t T) {
+    const int64_t base = (int64_t)s->B * s->Hkv * beam_col_blocks(s, nb);
+    const int64_t tiles = beam_tiles(nb, P, T);
+    int64_t n = (kDecWgSlots + base - 1) / base;
+    if (n > tiles / kDecMinTiles) n = tiles / kDecMinTiles;
+    return n < 1 ? 1 : (int)n;
+}
+
+int attn_fwd_beams(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* kp, const smt_attn_tensor* vp,
+                   const smt_attn_tensor* kg, const smt_attn_tensor* vg, const smt_attn_tensor* o, float* lse,
+                   const uint64_t* prompt_mask, int64_t prompt_mask_ld, const uint8_t* anc, int64_t anc_ld, int32_t nb,
+                   int32_t P, int32_t P_cap, int32_t T, int32_t T_cap, int32_t num_splits, void* workspace,
+                   const smt_attn_shape* shape, hipStream_t stream) {
+    int rc;
+    if ((rc = check_beams(fn, shape, nb, P, T)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(kg, "k_gen", fn)) ||
+        (rc = check_tensor(vg, "v_gen", fn)) || (rc = check_tensor(o, "o", fn)))
+        return rc;
+    // the prompt segment may be absent (P == 0: its tensors are never touched, their ptr may be null)
+    if (!kp || !vp) return fail(-1, "%s: null %s", fn, !kp ? "k_prompt" : "v_prompt");
+    if (P > 0 && ((rc = check_tensor(kp, "k_prompt", fn)) || (rc = check_tensor(vp, "v_prompt", fn)))) return rc;
+    if (!anc) return fail(-1, "%s: null anc", fn);
+    if (P > P_cap) return fail(-1, "%s: P %d > P_cap %d", fn, (int)P, (int)P_cap);
+    if (T > T_cap) return fail(-1, "%s: T %d > T_cap %d", fn, (int)T, (int)T_cap);
+    if (anc_ld < T) return fail(-1, "%s: anc_ld %lld < T %d", fn, (long long)anc_ld, (int)T);
+    if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
+    if ((rc = check_kmask_ld(fn, prompt_mask, prompt_mask_ld, P, "P"))) return rc;
+    const int nsplit = num_splits ? num_splits : beam_default_splits(shape, nb, P, T);
+    if (nsplit > 65535) return fail(-1, "%s: num_splits = %d is above 65535", fn, nsplit);
+    if (nsplit > 1 && !workspace)
+        return fail(-1, "%s: null workspace with %d splits (smt_attn_beams_workspace bytes)", fn, nsplit);
+    if (nsplit > 1 && !al16(workspace)) return fail(-2, "%s: workspace needs 16-byte alignment", fn);
+    // a tile's 64 rows are addressed with 32-bit byte offsets from the head's first row
+    const auto span = [](int rows, int64_t ss) { return ((int64_t)rows + kKV) * ss * 2 >= 0x7fffffffLL; };
+    if (P > 0 && (span(P, kp->ss) || span(P, vp->ss)))
+        return fail(-2, "%s: the P rows of k_prompt / v_prompt of one head must span less than 2 GiB", fn);
+    if (span(T, kg->ss) || span(T, vg->ss))
+        return fail(-2, "%s: the T rows of k_gen / v_gen of one head must span less than 2 GiB", fn);
+    const int G = shape->Hq / shape->Hkv;
+    const int64_t bh = (int64_t)shape->B * shape->Hkv;
+    BeamArgs a;
+    a.q = tns(q); a.q.ss = q->sb; a.q.sb = q->sb * nb;         // the beam as the "query position" of sample n
+    a.k = P > 0 ? tns(kp) : Tns{nullptr, 0, 0, 0}; a.v = P > 0 ? tns(vp) : Tns{nullptr, 0, 0, 0};
+    a.kg = tns(kg); a.vg = tns(vg);
+    a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o->sb * nb; a.o_sh = o->sh; a.o_ss = o->sb;
+    a.lse = lse;
+    a.kmask = P > 0 ? prompt_mask : nullptr; a.kmask_ld = prompt_mask_ld;
+    a.ws = static_cast<float*>(workspace);
+    a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.G = G;
+    a.Sq = nb; a.q_offset = 0;
+    a.ncols = nb * G; a.ncb = beam_col_blocks(shape, nb); a.nsplit = nsplit;
+    a.anc = anc; a.anc_ld = anc_ld;
+    a.nb = nb; a.P = P; a.T = T;
+    a.pt = (P + kKV - 1) / kKV; a.gt = (T + kKV - 1) / kKV;
+    a.tps = (beam_tiles(nb, P, T) + nsplit - 1) / nsplit;
+    a.sl2 = shape->scale * 1.4426950408889634f;
+    const dim3 grid((unsigned)a.ncb, (unsigned)nsplit, (unsigned)bh);
+    dispatch(shape->dtype, [&](auto f, auto km, auto direct) {
+        hipLaunchKernelGGL((attn_beams_kernel<km(), f(), direct()>), grid, dim3(64), 0, stream, a);
+    }, a.kmask != nullptr, nsplit == 1);
+    if ((rc = check_launch("attn_beams_kernel")) || nsplit == 1) return rc;
+    const dim3 cgrid((unsigned)a.ncols, (unsigned)bh);
+    dispatch(shape->dtype, [&](auto f) {
+        hipLaunchKernelGGL((attn_decode_combine_kernel<f(), true>), cgrid, dim3(kD), 0, stream, static_cast<const DecArgs&>(a));
+    });
+    return check_launch("attn_decode_combine_kernel");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1937,6 +2274,29 @@ int smt_attn_fwd_cached_pos(const smt_attn_tensor* q, const smt_attn_tensor* k, 
                             void* workspace, const smt_attn_shape* shape, hipStream_t stream) {
     return attn_fwd_cached("smt_attn_fwd_cached_pos", q, k, v, o, lse, key_mask, key_mask_ld, Sq, 0, positions,
                            positions_stride, true, num_splits, workspace, shape, stream);
+}
+
+int smt_attn_beams_splits(const smt_attn_shape* shape, int32_t nb, int32_t P, int32_t T) {
+    int rc;
+    if ((rc = check_beams("smt_attn_beams_splits", shape, nb, P, T))) return rc;
+    return beam_default_splits(shape, nb, P, T);
+}
+
+int64_t smt_attn_beams_workspace(const smt_attn_shape* shape, int32_t nb, int32_t P, int32_t T, int32_t num_splits) {
+    const char* fn = "smt_attn_beams_workspace";
+    int rc;
+    if ((rc = check_beams(fn, shape, nb, P, T))) return rc;
+    if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
+    return dec_workspace(shape, nb, num_splits ? num_splits : beam_default_splits(shape, nb, P, T));
+}
+
+int smt_attn_fwd_beams(const smt_attn_tensor* q, const smt_attn_tensor* k_prompt, const smt_attn_tensor* v_prompt,
+                       const smt_attn_tensor* k_gen, const smt_attn_tensor* v_gen, const smt_attn_tensor* o, float* lse,
+                       const uint64_t* prompt_mask, int64_t prompt_mask_ld, const uint8_t* anc, int64_t anc_ld,
+                       int32_t nb, int32_t P, int32_t P_cap, int32_t T, int32_t T_cap, int32_t num_splits,
+                       void* workspace, const smt_attn_shape* shape, hipStream_t stream) {
+    return attn_fwd_beams("smt_attn_fwd_beams", q, k_prompt, v_prompt, k_gen, v_gen, o, lse, prompt_mask, prompt_mask_ld,
+                          anc, anc_ld, nb, P, P_cap, T, T_cap, num_splits, workspace, shape, stream);
 }
 
 }  // extern "C"

@@ -1130,6 +1130,105 @@ def flash_attention_cached(q, k, v, scale=None, key_mask: "KeyMask" = None, q_of
     return (o, lse) if return_lse else o
 
 
+def flash_attention_beams(q, k_prompt, v_prompt, k_gen, v_gen, ancestors, num_beams, prompt_len, gen_len,
+                          prompt_key_mask: "KeyMask" = None, scale=None, num_splits: int = None,
+                          return_lse: bool = False):
+    """One decode position of beam search against a beam-shared cache, forward only
+    (``smt_attn_fwd_beams``, include/smt_attention.h): N samples x ``num_beams`` beams, row
+    ``r = n * num_beams + beam``. q ``[N * nb, Hq, 1, 128]``; k_prompt / v_prompt ``[N, Hkv, P_cap, 128]``
+    (the prompt once per sample, ``prompt_len <= P_cap`` keys valid); k_gen / v_gen
+    ``[N * nb, Hkv, T_cap, 128]`` (row = physical slot, position = generation step, ``gen_len <= T_cap``
+    steps valid, the current token's included); ``ancestors`` uint8 ``[N * nb, >= gen_len]``:
+    ``ancestors[r, j]`` is the slot (0..nb-1) of r's sample that holds the step-j key of row r's
+    hypothesis -> ``[N * nb, 1, Hq, 128]``. Row r sees prompt key j iff ``prompt_key_mask`` (a
+    :class:`KeyMask` whose ``bits`` are ``[N, >= ceil(prompt_len / 64)]``, rows of any stride; None:
+    every key) keeps it, and generated entry (slot s, step j) iff ``ancestors[r, j] == s``; generated
+    entries have no mask of their own. Any strides with head_dim innermost. K / V rows past
+    ``prompt_len`` / ``gen_len`` are never read, and no address depends on a value in ``ancestors`` (a
+    value >= nb matches nothing; a row that sees no key at all gets zeros and lse = +inf).
+    ``num_splits``, ``return_lse`` (fp32 ``[N * nb, Hq]``, log2 units): as in
+    :func:`flash_attention_cached`. ``prompt_len`` and ``gen_len`` are host integers; nothing
+    synchronises with the host. There is no backward: an input that requires grad while gradients are
+    enabled raises."""
+    tensors = (q, k_prompt, v_prompt, k_gen, v_gen)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise NotImplementedError("flash_attention_beams: beam-shared attention has no backward (inference only); run "
+                                  "under torch.no_grad() or detach the inputs")
+    for t, n in zip(tensors, ("q", "k_prompt", "v_prompt", "k_gen", "v_gen")):
+        _need(t, "beam-shared flash attention " + n, like=q)
+    nb, P, T = int(num_beams), int(prompt_len), int(gen_len)
+    if any(t.dim() != 4 for t in tensors) or v_prompt.shape != k_prompt.shape or v_gen.shape != k_gen.shape:
+        raise NotImplementedError("beam-shared flash attention: 4-D q, k_prompt / v_prompt and k_gen / v_gen of equal "
+                                  f"shapes (q {tuple(q.shape)}, k_prompt {tuple(k_prompt.shape)}, v_prompt "
+                                  f"{tuple(v_prompt.shape)}, k_gen {tuple(k_gen.shape)}, v_gen {tuple(v_gen.shape)})")
+    R, Hq, Sq, D = q.shape
+    Hkv, T_cap = k_gen.shape[1], k_gen.shape[2]
+    if nb < 1 or R % nb:
+        raise ValueError(f"beam-shared flash attention: {R} rows are no multiple of num_beams = {nb}")
+    N, P_cap = R // nb, k_prompt.shape[2]
+    if D != 128 or Sq != 1 or Hq % Hkv or k_gen.shape != (R, Hkv, T_cap, D) or k_prompt.shape != (N, Hkv, P_cap, D):
+        raise NotImplementedError(f"beam-shared flash attention: head_dim 128, one query position, Hq % Hkv == 0, "
+                                  f"k_prompt [N, Hkv, P_cap, 128], k_gen [N * nb, Hkv, T_cap, 128] (q {tuple(q.shape)}, "
+                                  f"k_prompt {tuple(k_prompt.shape)}, k_gen {tuple(k_gen.shape)}, nb {nb})")
+    if not 0 <= P <= P_cap or not 1 <= T <= T_cap:
+        raise ValueError(f"beam-shared flash attention: prompt_len {P} of {P_cap}, gen_len {T} of {T_cap} "
+                         "(gen_len counts the current token's key, so it is at least 1)")
+    anc = ancestors
+    if (not isinstance(anc, torch.Tensor) or anc.dtype != torch.uint8 or anc.device != q.device or anc.dim() != 2
+            or anc.shape[0] != R or anc.shape[1] < T):
+        raise ValueError(f"beam-shared flash attention: ancestors must be uint8 [{R}, >= {T}] on {q.device}")
+    if anc.stride(1) != 1:
+        anc = anc.contiguous()
+    num_splits = 0 if num_splits is None else int(num_splits)
+    if num_splits < 0:
+        raise ValueError(f"beam-shared flash attention: num_splits = {num_splits}")
+    q, k_gen, v_gen = _attn_ready(q), _attn_ready(k_gen), _attn_ready(v_gen)
+    if P:
+        k_prompt, v_prompt = _attn_ready(k_prompt), _attn_ready(v_prompt)
+    pm, pm_ld = None, 0
+    if prompt_key_mask is not None and P:
+        bits = prompt_key_mask.bits
+        if (bits.dim() != 2 or bits.dtype != torch.int64 or bits.device != q.device or bits.shape[0] != N
+                or bits.shape[1] < -(-P // 64) or prompt_key_mask.S < P):
+            raise ValueError(f"beam-shared flash attention: prompt key mask for [{bits.shape[0]}, {prompt_key_mask.S}] "
+                             f"keys, the prompt segment has [{N}, {P}]")
+        if bits.stride(1) != 1:
+            bits = bits.contiguous()
+        pm, pm_ld = bits.data_ptr(), bits.stride(0) if N > 1 else bits.shape[1]
+    o = torch.empty(R, 1, Hq, D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(R, Hq, dtype=torch.float32, device=q.device) if return_lse else None
+    shape = _hip.AttnShape(N, Hq, Hkv, P + T, float(scale if scale is not None else D ** -0.5), _dt(q))
+    lib = _hip.load()
+    if num_splits == 0:
+        num_splits = lib.smt_attn_beams_splits(ctypes.byref(shape), nb, P, T)
+        _hip._check(min(num_splits, 0), "smt_attn_beams_splits")
+    ws_bytes = lib.smt_attn_beams_workspace(ctypes.byref(shape), nb, P, T, num_splits)
+    _hip._check(min(ws_bytes, 0), "smt_attn_beams_workspace")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes else None
+    with torch.cuda.device(q.device):
+        rc = lib.smt_attn_fwd_beams(_attn_ref(q), _attn_ref(k_prompt), _attn_ref(v_prompt), _attn_ref(k_gen),
+                                    _attn_ref(v_gen), _attn_ref(o.transpose(1, 2)), _hip._ptr(lse), pm, pm_ld,
+                                    anc.data_ptr(), anc.stride(0) if R > 1 else anc.shape[1], nb, P, P_cap, T, T_cap,
+                                    num_splits, _hip._ptr(ws), ctypes.byref(shape), _stream(q))
+    _hip._check(rc, "smt_attn_fwd_beams")
+    return (o, lse) if return_lse else o
+
+
+def _beam_decode(layer, query, attention_mask, scaling):
+    """A decode step on a :class:`~sparse_matrix_tuning_amd.beam_cache.BeamSharedCache`: ``layer`` is the
+    cache layer that tagged the K / V its ``update`` returned. The prompt's key mask is the
+    :class:`CacheMask`'s, rows ``[::nb]`` and the words of the first ``prompt_len`` keys (a view: the
+    beams of a sample share their padding); the columns of generated positions are not consulted."""
+    if attention_mask is not None and not isinstance(attention_mask, CacheMask):
+        raise NotImplementedError("smt_flash attention: a decode step on a BeamSharedCache takes the CacheMask "
+                                  f"smt_flash_mask builds (got {type(attention_mask).__name__})")
+    nb, P = layer.state.num_beams, layer.prompt_len
+    km = attention_mask.key_mask if attention_mask is not None else None
+    pm = KeyMask(km.bits[::nb, :-(-P // 64)], P) if km is not None else None
+    return flash_attention_beams(query, layer.k_prompt, layer.v_prompt, layer.k_gen, layer.v_gen, layer.state.anc, nb, P,
+                                 layer.steps, prompt_key_mask=pm, scale=scaling)
+
+
 def smt_flash_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None,
                                 is_causal=None, **kwargs):
     """transformers attention-function signature (``AttentionInterface``). Causal self-attention,
@@ -1142,7 +1241,10 @@ def smt_flash_attention_forward(module, query, key, value, attention_mask, dropo
     keys) runs :func:`flash_attention_cached`, forward only: dropout or a :class:`DocMask` with a
     cache raises. A tensor ``q_offset`` in the :class:`CacheMask` (a decode step on a static cache) is
     passed through to the kernel; the first forward on a static cache (``CacheMask.prefill``) runs the
-    training forward kernel on the first ``Sq`` rows of the buffer.
+    training forward kernel on the first ``Sq`` rows of the buffer. A decode step on a
+    :class:`~sparse_matrix_tuning_amd.beam_cache.BeamSharedCache` (its ``update`` tags the K / V it returns
+    with the cache layer) runs :func:`flash_attention_beams` on that layer's buffers; without that cache
+    nothing changes.
     Every same-length call goes to :func:`flash_attention` with ``any_length=True``: the
     reference's collator pads a batch to its longest sample (helper.py:191-205), so S is any integer in
     training, in the evaluation loss and in the prefill of ``generate()``. A gradient-free call takes
@@ -1157,6 +1259,11 @@ def smt_flash_attention_forward(module, query, key, value, attention_mask, dropo
     Sq, Skv = query.shape[2], key.shape[2]
     cached = isinstance(attention_mask, CacheMask) or Sq != Skv
     dropout = float(dropout or 0.0)
+    beam_layer = getattr(key, "_smt_beam", None)
+    if beam_layer is not None:                     # a decode step on a BeamSharedCache (its update tags K / V)
+        if dropout != 0.0:
+            raise NotImplementedError("smt_flash attention: dropout with a KV cache (the beam kernel is inference only)")
+        return _beam_decode(beam_layer, query, attention_mask, scaling), None
     if cached:
         if dropout != 0.0:
             raise NotImplementedError("smt_flash attention: dropout with a KV cache (the cached kernel is inference only)")
