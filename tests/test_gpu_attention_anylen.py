@@ -24,7 +24,8 @@ from sparse_matrix_tuning_amd.fused_llama import (DocMask, KeyMask, dropout_effe
                                                   flash_dropout_mask, smt_flash_attention_forward, smt_flash_mask)
 from tests import test_gpu_attention as plain
 from tests import test_gpu_attention_packed as pref
-from tests.attn_ref import D, DEV, allowed_causal, allowed_docs, eager16, inputs, ref32, rel as _rel
+from tests.attn_ref import (D, DEV, allowed_causal, allowed_docs, check_outputs, eager16, inputs, ref32, ref64_bounds,
+                            rel as _rel)
 
 pytestmark = pytest.mark.gpu
 LENGTHS = [1, 3, 33, 66, 130, 259, 517]
@@ -32,6 +33,11 @@ LENGTHS = [1, 3, 33, 66, 130, 259, 517]
 
 def _inputs(B, Hq, Hkv, S, layout="hf", dtype=torch.bfloat16, seed=0):
     return inputs(B, Hq, Hkv, S, layout, dtype, seed + S + Hq)
+
+
+def _per_element(what, o, lse, dq, dk, dv, R):
+    """Beside the Frobenius bars: every element within its derived bound (DESIGN, "The bar on attention")."""
+    check_outputs(what, {"o": o, "dq": dq, "dk": dk, "dv": dv, "lse2": lse}, R)
 
 
 def _run(q, k, v, g, **kw):
@@ -65,6 +71,7 @@ def test_any_length_matches_fp32_reference(B, Hq, Hkv, S, layout, dtype):
         assert torch.isfinite(mine.float()).all(), name
         assert e <= max(8e-3, 1.5 * es), (name, e, es)
     assert (lse - rlse).abs().max().item() < 2e-3
+    _per_element(f"S {S} {layout}", o, lse, dq, dk, dv, ref64_bounds(q, k, v, g, D ** -0.5, allowed_causal(S)))
 
 
 @pytest.mark.parametrize("S", [66, 259])
@@ -92,6 +99,7 @@ def test_any_length_key_mask(S):
     assert not vis[1, :, :3].any() and (o[1, :3].float() == 0).all() and (dq[1, :, :3].float() == 0).all()
     dead = ~keep[:, None, :, None].expand(B, Hkv, S, D)
     assert (dk.float()[dead] == 0).all() and (dv.float()[dead] == 0).all()
+    _per_element(f"S {S} key mask", o, lse, dq, dk, dv, ref64_bounds(q, k, v, g, D ** -0.5, allowed_causal(S, keep)))
 
 
 @pytest.mark.parametrize("S", [66, 259])
@@ -111,6 +119,7 @@ def test_any_length_dropout(S, p):
         assert torch.isfinite(mine.float()).all(), name
         assert e <= max(8e-3, 1.5 * es), (name, e, es)
     assert (lse - rlse).abs().max().item() < 2e-3       # lse is untouched by dropout
+    _per_element(f"S {S} p {p}", o, lse, dq, dk, dv, ref64_bounds(q, k, v, g, D ** -0.5, allowed_causal(S), M, r))
 
 
 @pytest.mark.parametrize("p", [0.1, 0.5])
@@ -137,6 +146,7 @@ def test_any_length_documents(S, rows):
         assert torch.isfinite(mine.float()).all(), name
         assert e <= max(8e-3, 1.5 * es), (name, e, es)
     assert torch.isfinite(lse).all()
+    _per_element(f"S {S} documents", o, lse, dq, dk, dv, ref64_bounds(q, k, v, g, D ** -0.5, allowed))
     assert (lse - rlse).abs().max().item() < 2e-3
 
 
