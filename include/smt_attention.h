@@ -294,6 +294,46 @@ int     smt_attn_fwd_beams(const smt_attn_tensor* q, const smt_attn_tensor* k_pr
                            int64_t anc_ld, int32_t nb, int32_t P, int32_t P_cap, int32_t T, int32_t T_cap,
                            int32_t num_splits, void* workspace, const smt_attn_shape* shape, hipStream_t stream);
 
+/*
+ * The same call with the number of generated positions on the device (additive; the ABI version is
+ * unchanged): for capturing a beam-search decode step in a HIP graph: no launch parameter depends on
+ * the step.
+ *   steps   int32 device memory, 4-byte aligned, ONE counter for the whole call: the number of
+ *           generated positions, the current token's included; read by the kernel (never by the host)
+ *   anc_ld  >= T_cap
+ * The kernel SATURATES T = clamp(*steps, 1, T_cap) before it forms any address, and derives from T what
+ * smt_attn_fwd_beams derives from its T on the host: ceil(T / 64) tiles per slot, the tile list (the
+ * prompt's tiles, then every slot's), ceil(tiles / num_splits) tiles per split, the buffer descriptors
+ * that end at row T - 1 and the j < T test on the ancestry bytes. For a given num_splits the result is
+ * BIT-IDENTICAL to smt_attn_fwd_beams with T = clamp(*steps, 1, T_cap) on the same tensors. The grid,
+ * num_splits == 0 (smt_attn_beams_splits(shape, nb, P, T_cap)) and the workspace
+ * (smt_attn_beams_workspace(shape, nb, P, T_cap, num_splits)) are sized from the capacity; a split that
+ * ends up without tiles writes the empty partial, so a cache far from full runs more, emptier splits
+ * than the host-T call. No read or write outside the tensors depends on *steps or on a value in anc.
+ *
+ * Returns before any HIP call: -1 for what smt_attn_fwd_beams refuses with T read as T_cap, for null
+ * steps and for anc_ld < T_cap; -2 for steps that are not 4-byte aligned, and for the 2 GiB extents
+ * taken at T_cap.
+ */
+int     smt_attn_fwd_beams_pos(const smt_attn_tensor* q, const smt_attn_tensor* k_prompt, const smt_attn_tensor* v_prompt,
+                               const smt_attn_tensor* k_gen, const smt_attn_tensor* v_gen, const smt_attn_tensor* o,
+                               float* lse, const uint64_t* prompt_mask, int64_t prompt_mask_ld, const uint8_t* anc,
+                               int64_t anc_ld, int32_t nb, int32_t P, int32_t P_cap, const int32_t* steps, int32_t T_cap,
+                               int32_t num_splits, void* workspace, const smt_attn_shape* shape, hipStream_t stream);
+
+/*
+ * One step's K and V into the generated buffers, with the same counter and the same saturation: k_new,
+ * v_new [rows][Hkv][1][128] (any sb / sh, d-stride 1, 16-byte aligned rows; ss is not used) are written
+ * to row clamp(*steps, 1, T_cap) - 1 of k_gen, v_gen [rows][Hkv][T_cap][128], both in one launch, with
+ * 16-byte stores; no other row is touched, and the row cannot leave the buffers whatever *steps holds.
+ * dtype: SMT_DTYPE_BF16 or SMT_DTYPE_FP16 (the elements are copied as 16-bit words).
+ * Returns before any HIP call: -1 for a null tensor or steps, a dtype that is not a 16-bit format,
+ * rows / Hkv / T_cap < 1; -2 for misaligned rows and for steps that are not 4-byte aligned.
+ */
+int     smt_attn_kv_append_pos(const smt_attn_tensor* k_new, const smt_attn_tensor* v_new, const smt_attn_tensor* k_gen,
+                               const smt_attn_tensor* v_gen, const int32_t* steps, int32_t rows, int32_t Hkv,
+                               int32_t T_cap, int32_t dtype, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

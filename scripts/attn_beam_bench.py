@@ -18,8 +18,20 @@ times (default 2), and one ``"impl": "ratio"`` line per (P, T, round) divides th
 fast enough), ``kernel_us`` = the summed device time of the kernels one call launches (torch.profiler),
 ``kernels`` = that sum by kernel. ``rel_diff`` (kernel lines): the two kernels' results against each
 other. Every call takes the next of a ring of K / V copies larger than the 256 MB Infinity Cache, as
-the layers of a model do, so the bytes come from HBM (``kv_copies``)."""
+the layers of a model do, so the bytes come from HBM (``kv_copies``).
+
+``--pos`` times the device-counter form in place of the DynamicCache comparison (T is then a fill level
+of the ``--T-cap`` buffers; profiles/r15_beam_decode_step_pos.jsonl):
+  ``beam_kernel``        as above: host T, the default split count of (P, T)
+  ``beam_kernel@cap``    host T at the split count the capacity gives (``splits``), which is what the
+                         device-counter call runs with: the cost of the capacity-sized split count alone
+  ``beam_kernel_pos``    flash_attention_beams with gen_len a device tensor (smt_attn_fwd_beams_pos)
+  ``beam_step``          ancestry update + two slice copies + the host-T kernel
+  ``beam_step_pos``      ancestry update + kv_append (smt_attn_kv_append_pos) + the device-counter kernel
+and one ``"impl": "pos_ratio"`` line per (P, T, round). ``bit_identical``: beam_kernel_pos against
+beam_kernel@cap on the same buffers."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -27,7 +39,8 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sparse_matrix_tuning_amd.fused_llama import flash_attention_beams, flash_attention_cached  # noqa: E402
+from sparse_matrix_tuning_amd import _hip  # noqa: E402
+from sparse_matrix_tuning_amd.fused_llama import flash_attention_beams, flash_attention_cached, kv_append  # noqa: E402
 from attn_decode_bench import kernel_us, timed  # noqa: E402
 
 
@@ -40,6 +53,70 @@ def genealogy(N, nb, T, T_cap, seed):
     for t in range(1, T):
         anc[:, :t] = anc[base + torch.randint(0, nb, (R,), generator=g)][:, :t]
     return anc.cuda()
+
+
+def pos_legs(a, N, nb, Hq, Hkv, P, T, T_cap, anc, beam_idx, mk):
+    """The --pos legs of one (P, T): host T against the device counter, kernel alone and whole step."""
+    R, D = N * nb, 128
+    n = max(2, int(a.ring_bytes // (2 * (N * P + R * T_cap) * Hkv * D * 2)))
+    ring = [(mk(N, Hkv, P, D), mk(N, Hkv, P, D), mk(R, Hkv, T_cap, D), mk(R, Hkv, T_cap, D)) for _ in range(n)]
+    q = mk(R, 1, Hq, D).transpose(1, 2)
+    k_new, v_new = mk(R, 1, Hkv, D).transpose(1, 2), mk(R, 1, Hkv, D).transpose(1, 2)
+    cnt = torch.tensor([T], dtype=torch.int32, device="cuda")
+    shape = _hip.AttnShape(N, Hq, Hkv, P + T_cap, D ** -0.5, _hip.DTYPE_BF16)
+    lib = _hip.load()
+    ns_cap = lib.smt_attn_beams_splits(ctypes.byref(shape), nb, P, T_cap)
+    ns_own = lib.smt_attn_beams_splits(ctypes.byref(shape), nb, P, T)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % n
+        return state["i"]
+
+    def reorder():
+        if T > 1:
+            anc[:, :T - 1] = anc.index_select(0, beam_idx)[:, :T - 1]
+
+    def beam_step():
+        kp, vp, kg, vg = ring[nxt()]
+        reorder()
+        kg[:, :, T - 1:T].copy_(k_new)
+        vg[:, :, T - 1:T].copy_(v_new)
+        return flash_attention_beams(q, kp, vp, kg, vg, anc, nb, P, T)
+
+    def beam_step_pos():
+        kp, vp, kg, vg = ring[nxt()]
+        reorder()
+        kv_append(k_new, v_new, kg, vg, cnt)
+        return flash_attention_beams(q, kp, vp, kg, vg, anc, nb, P, cnt)
+
+    impls = [("beam_kernel", lambda: flash_attention_beams(q, *ring[nxt()], anc, nb, P, T)),
+             ("beam_kernel@cap", lambda: flash_attention_beams(q, *ring[nxt()], anc, nb, P, T, num_splits=ns_cap)),
+             ("beam_kernel_pos", lambda: flash_attention_beams(q, *ring[nxt()], anc, nb, P, cnt)),
+             ("beam_step", beam_step), ("beam_step_pos", beam_step_pos)]
+    same = bool(torch.equal(flash_attention_beams(q, *ring[0], anc, nb, P, cnt),
+                            flash_attention_beams(q, *ring[0], anc, nb, P, T, num_splits=ns_cap)))
+    anc0 = anc.clone()
+    for rnd in range(a.rounds):
+        res = {}
+        for name, f in impls:
+            us = timed(f, a.iters)
+            k_us, kernels = kernel_us(f, min(a.iters, 50))
+            anc.copy_(anc0)
+            res[name] = (us, k_us)
+            print(json.dumps({"impl": name, "round": rnd, "N": N, "nb": nb, "Hq": Hq, "Hkv": Hkv, "P": P, "T": T,
+                              "T_cap": T_cap, "splits": ns_own if name in ("beam_kernel", "beam_step") else ns_cap,
+                              "us": round(us, 2), "kernel_us": round(k_us, 2), "kv_copies": n, "kernels": kernels,
+                              "bit_identical": same}), flush=True)
+        k = lambda name: res[name][1]
+        print(json.dumps({"impl": "pos_ratio", "round": rnd, "P": P, "T": T, "T_cap": T_cap,
+                          "splits_own": ns_own, "splits_cap": ns_cap,
+                          "kernel_us_pos_minus_host": round(k("beam_kernel_pos") - k("beam_kernel"), 2),
+                          "kernel_us_cap_splits_minus_own": round(k("beam_kernel@cap") - k("beam_kernel"), 2),
+                          "kernel_us_pos_minus_cap_splits": round(k("beam_kernel_pos") - k("beam_kernel@cap"), 2),
+                          "kernel_us_pos_over_host": round(k("beam_kernel_pos") / k("beam_kernel"), 3),
+                          "step_kernel_us_pos_over_host": round(k("beam_step_pos") / k("beam_step"), 3),
+                          "step_us_pos_over_host": round(res["beam_step_pos"][0] / res["beam_step"][0], 3)}), flush=True)
 
 
 def main():
@@ -55,6 +132,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--splits", type=int, nargs="*", default=[], help="forced split counts of the beam kernel to time "
                     "beside the default (impl beam_kernel@N)")
+    ap.add_argument("--pos", action="store_true", help="the device-counter legs (smt_attn_fwd_beams_pos, "
+                    "smt_attn_kv_append_pos) against host T, in place of the DynamicCache comparison")
     ap.add_argument("--ring-bytes", type=float, default=1.5e9, help="total bytes of the K/V copies a run cycles through")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -72,6 +151,9 @@ def main():
             dyn_bytes = 2 * R * Hkv * (P + T) * D * 2
             n = max(2, int(a.ring_bytes // dyn_bytes))
             # the beam-shared buffers, and the per-row cache a DynamicCache holds for the same hypotheses
+            if a.pos:
+                pos_legs(a, N, nb, Hq, Hkv, P, T, T_cap, anc, beam_idx, mk)
+                continue
             beam_ring = [(mk(N, Hkv, P, D), mk(N, Hkv, P, D), mk(R, Hkv, T_cap, D), mk(R, Hkv, T_cap, D)) for _ in range(n)]
             src = base[:, None] + anc[:, :T].long()
             step = torch.arange(T, device="cuda")[None, :]

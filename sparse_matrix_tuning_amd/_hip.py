@@ -47,6 +47,7 @@ ABI_FUNCTIONS = (
     "smt_attn_cached_splits", "smt_attn_cached_workspace", "smt_attn_fwd_cached",
     "smt_attn_fwd_cached_pos",
     "smt_attn_beams_splits", "smt_attn_beams_workspace", "smt_attn_fwd_beams",
+    "smt_attn_fwd_beams_pos", "smt_attn_kv_append_pos",
     "smt_fp8_last_error", "smt_quant_rows_e4m3", "smt_quant_cols_t_e4m3", "smt_quant_rows_cat_e4m3",
     "smt_swiglu_fwd_quant_e4m3", "smt_swiglu_bwd_quant_e4m3", "smt_swiglu_bwd_quant_e4m3_packed",
     "smt_rmsnorm_fwd_quant_e4m3",
@@ -188,6 +189,9 @@ _SIGS = {
     "smt_attn_beams_workspace": (_I64, [ctypes.POINTER(AttnShape), _I32, _I32, _I32, _I32]),
     "smt_attn_fwd_beams": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 6 + [_P, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32,
                                           _I32, _I32, _P, ctypes.POINTER(AttnShape), _P]),
+    "smt_attn_fwd_beams_pos": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 6 + [_P, _P, _I64, _P, _I64, _I32, _I32, _I32, _P,
+                                              _I32, _I32, _P, ctypes.POINTER(AttnShape), _P]),
+    "smt_attn_kv_append_pos": (ctypes.c_int, [ctypes.POINTER(AttnTensor)] * 4 + [_P, _I32, _I32, _I32, _I32, _P]),
     "smt_model_ops_last_error": (ctypes.c_char_p, []),
     "smt_rmsnorm_fwd": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _I32, ctypes.c_float, _I32, _P]),
     "smt_rmsnorm_bwd_waves": (ctypes.c_int, [_I64]),

@@ -10,7 +10,15 @@ table and nothing else; the decode attention (``smt_attn_fwd_beams``, include/sm
 through ``smt_flash`` on a :func:`~sparse_matrix_tuning_amd.fused_llama.patch_llama`-ed model) reads
 every physical row once per sample and decides by comparison which beam sees it.
 
-The bookkeeping here is plain torch and runs on CPU tensors as well (tests/test_attention_beams_host.py).
+With ``device_steps=True`` the number of generated positions also lives in ONE int32 counter on the
+device, shared by all layers: ``update`` appends through ``smt_attn_kv_append_pos`` at the row the
+counter names and returns the whole buffers, and the attention (``smt_attn_fwd_beams_pos``) reads the
+counter itself, so no launch parameter of a decode step depends on the step and the step can be
+captured in a graph and replayed (``graph=True``: the decode runner of
+:mod:`~sparse_matrix_tuning_amd.fused_llama` does that on a ``patch_llama``-ed model).
+
+The bookkeeping here is plain torch and runs on CPU tensors as well (tests/test_attention_beams_host.py,
+tests/test_attention_beams_pos_host.py).
 """
 from __future__ import annotations
 
@@ -20,12 +28,17 @@ from transformers.cache_utils import Cache, CacheLayerMixin
 
 class _BeamState:
     """What the layers of one :class:`BeamSharedCache` share: the beam count, the capacity and the
-    ancestry table (allocated by the first prefill ``update``)."""
+    ancestry table (allocated by the first prefill ``update``). With ``device_steps``: also the int32
+    counter of generated positions (the current token's included; allocated with the table, advanced
+    once per forward) and the prompt's key-mask words (built at the first decode step)."""
 
-    def __init__(self, num_beams: int, max_new_tokens: int):
+    def __init__(self, num_beams: int, max_new_tokens: int, device_steps: bool = False):
         self.num_beams, self.capacity = int(num_beams), int(max_new_tokens)
         self.anc = None                    # uint8 [N * nb, capacity]
         self.reorders = 0                  # ancestry updates so far (one per generated token)
+        self.device_steps = bool(device_steps)
+        self.counter = None                # int32 [1] (device_steps)
+        self.prompt_mask = None            # (KeyMask or None,) once the first decode step has built it
 
     def ensure(self, rows: int, device) -> None:
         if self.anc is None:
@@ -33,6 +46,8 @@ class _BeamState:
             # reorder hands the row another hypothesis, and reorders only touch the steps written so far
             own = (torch.arange(rows, device=device) % self.num_beams).to(torch.uint8)
             self.anc = own[:, None].repeat(1, self.capacity).contiguous()
+            if self.device_steps:
+                self.counter = torch.zeros(1, dtype=torch.int32, device=device)
         elif self.anc.shape[0] != rows or self.anc.device != device:
             raise ValueError(f"BeamSharedCache: {rows} rows on {device}, the ancestry table has "
                              f"{self.anc.shape[0]} on {self.anc.device}")
@@ -46,9 +61,10 @@ class BeamSharedLayer(CacheLayerMixin):
     is_compileable = False
     is_sliding = False
 
-    def __init__(self, state: _BeamState):
+    def __init__(self, state: _BeamState, index: int = 0):
         super().__init__()
         self.state = state
+        self.index = index                 # layer 0 advances the shared device counter
         self.k_prompt = self.v_prompt = self.k_gen = self.v_gen = None
         self.prompt_len = 0
         self.steps = 0
@@ -74,7 +90,8 @@ class BeamSharedLayer(CacheLayerMixin):
         """The prefill (the first call) stores rows ``[::nb]`` as the prompt segment and returns its
         inputs: the prefill attention is the same-length call it always was. A decode call writes the
         step's K / V into the generated buffers in place (no ``cat``) and returns views of them that
-        carry this layer as ``_smt_beam``, which is what ``smt_flash`` routes on."""
+        carry this layer as ``_smt_beam``, which is what ``smt_flash`` routes on. With ``device_steps``
+        the decode call goes through :meth:`_update_device_steps` and returns the whole buffers."""
         if not self.is_initialized:
             self.lazy_initialization(key_states, value_states)
             return key_states, value_states
@@ -86,10 +103,33 @@ class BeamSharedLayer(CacheLayerMixin):
         t = self.steps
         if t >= self.state.capacity:
             raise RuntimeError(f"BeamSharedCache: max_new_tokens = {self.state.capacity} generated positions are full")
+        if self.state.device_steps:
+            return self._update_device_steps(key_states, value_states)
         self.k_gen[:, :, t:t + 1].copy_(key_states)
         self.v_gen[:, :, t:t + 1].copy_(value_states)
         self.steps = t + 1
         k, v = self.k_gen[:, :, :t + 1], self.v_gen[:, :, :t + 1]
+        k._smt_beam = v._smt_beam = self
+        return k, v
+
+    def _update_device_steps(self, key_states, value_states):
+        """The decode ``update`` with the counter on the device: layer 0 advances it (once per forward),
+        every layer appends at row ``clamp(counter, 1, capacity) - 1`` and returns the WHOLE buffers,
+        tagged; the attention reads the counter. The host's ``steps`` follows for ``get_seq_length``,
+        the capacity check above and ``reorder_cache``. Nothing here depends on the step but that
+        count, so the launches of one step are those of every step."""
+        st = self.state
+        if self.index == 0:
+            st.counter.add_(1)
+        if self.k_gen.device.type == "cuda":
+            from .fused_llama import kv_append
+            kv_append(key_states, value_states, self.k_gen, self.v_gen, st.counter)
+        else:
+            row = st.counter.clamp(1, st.capacity).long() - 1
+            self.k_gen.index_copy_(2, row, key_states)
+            self.v_gen.index_copy_(2, row, value_states)
+        self.steps += 1
+        k, v = self.k_gen[:], self.v_gen[:]
         k._smt_beam = v._smt_beam = self
         return k, v
 
@@ -153,18 +193,30 @@ class BeamSharedCache(Cache):
     hundred bytes; K / V never move. ``beam_idx`` must stay within each sample's rows, as beam search's does.
     """
 
-    def __init__(self, config, num_beams: int, max_new_tokens: int):
+    def __init__(self, config, num_beams: int, max_new_tokens: int, device_steps: bool = False, graph: bool = False):
         if int(num_beams) < 1 or int(num_beams) > 255:
             raise ValueError(f"BeamSharedCache: num_beams = {num_beams} (1..255: slots are stored as uint8)")
         if int(max_new_tokens) < 1:
             raise ValueError(f"BeamSharedCache: max_new_tokens = {max_new_tokens}")
-        self.state = _BeamState(num_beams, max_new_tokens)
+        self.graph = bool(graph)
+        self.state = _BeamState(num_beams, max_new_tokens, device_steps=bool(device_steps) or self.graph)
+        self.graph_captures = self.graph_replays = 0       # the decode runner's (fused_llama.py)
+        self.decode_runner = None
         cfg = config.get_text_config(decoder=True) if hasattr(config, "get_text_config") else config
-        super().__init__(layers=[BeamSharedLayer(self.state) for _ in range(cfg.num_hidden_layers)])
+        super().__init__(layers=[BeamSharedLayer(self.state, i) for i in range(cfg.num_hidden_layers)])
 
     @property
     def num_beams(self) -> int:
         return self.state.num_beams
+
+    @property
+    def device_steps(self) -> bool:
+        return self.state.device_steps
+
+    @property
+    def steps_tensor(self):
+        """The int32 ``[1]`` counter of generated positions on the cache's device (``device_steps``), or None."""
+        return self.state.counter
 
     @property
     def ancestors(self):
@@ -191,8 +243,11 @@ class BeamSharedCache(Cache):
     def reset(self):
         for layer in self.layers:
             layer.reset()
-        self.state.anc = None
+        if self.state.counter is not None:
+            self.state.counter.zero_()                  # for whoever still holds it; a new one comes with the table
+        self.state.anc = self.state.counter = self.state.prompt_mask = None
         self.state.reorders = 0
+        self.decode_runner = None
 
     def crop(self, tokens_to_remove: int) -> None:
         raise NotImplementedError("BeamSharedCache: crop is not supported")

@@ -4,7 +4,9 @@
 // smt_attn_*_docs); and the forward-only split-KV kernel of calls against a KV cache (attn_decode_kernel,
 // smt_attn_fwd_cached; smt_attn_fwd_cached_pos with the query position read on the device, for a
 // pre-allocated cache; attn_beams_kernel, smt_attn_fwd_beams, one decode position of beam search against
-// a beam-shared cache that is never reordered). Any sequence length S >= 1, forward and backward: lse and delta are
+// a beam-shared cache that is never reordered; smt_attn_fwd_beams_pos with the number of generated
+// positions read on the device and smt_attn_kv_append_pos, which writes a step's K / V at that
+// position, for a decode step that is captured in a graph). Any sequence length S >= 1, forward and backward: lse and delta are
 // [B][Hq][lse_ld] with a row stride lse_ld % 4 == 0 of their own (smt_attn_fwd_ld / smt_attn_bwd_ld),
 // which is all the 16-byte lse / delta fetch of the dK/dV kernel needs; the other entry points are
 // these with lse_ld = S.
@@ -1536,6 +1538,9 @@ struct BeamArgs : DecArgs {                // DecArgs: q / o with sb = nb rows, 
     int64_t anc_ld;
     int nb, P, T, pt, gt;                  // pt / gt: 64-key tiles of the prompt / of one slot's generated rows
 };
+struct BeamPosArgs : BeamArgs {            // the device-counter form (BeamArgs itself keeps its size); T = T_cap here
+    const int32_t* steps;
+};
 
 struct BeamTile {
     int s, g;                              // s: the slot, -1 = the prompt; g: the tile within that segment
@@ -1558,9 +1563,28 @@ __device__ __forceinline__ uint64_t low_bits(int rem) { return rem >= 64 ? ~0ull
 
 constexpr int kBeamPre = 8;                // beams of a column block whose ancestry bytes are fetched a tile ahead
 
-template <bool KMASK, int F, bool DIRECT>
+// Args = BeamPosArgs (smt_attn_fwd_beams_pos): the number of generated positions is *a.steps, read
+// here and saturated into [1, T_cap] (a.T holds the capacity) before anything is derived from it, so no
+// address depends on an out-of-contract value. gt, the tile list and the tiles per split are then the
+// ones the host computes for that T, and the grid is sized from the capacity. The body reads the three
+// through gen_T() / gen_gt() / gen_tps(): the kernel's own values here, a.T, a.gt and a.tps as they are
+// with Args = BeamArgs. Selections on the constant POS and not locals or lambdas: with these the BeamArgs
+// instances compile to the instructions they had before this form existed (scripts/diag/isa_compare.py).
+template <bool KMASK, int F, bool DIRECT, class Args>
 __global__ __launch_bounds__(64)
-void attn_beams_kernel(BeamArgs a) {
+void attn_beams_kernel(Args a) {
+    constexpr bool POS = std::is_same<Args, BeamPosArgs>::value;
+    int T_dev = 0, gt_dev = 0, tps_dev = 0;
+    if constexpr (POS) {
+        int s = *a.steps;                                      // workgroup-uniform
+        s = s < 1 ? 1 : (s > a.T ? a.T : s);
+        T_dev = __builtin_amdgcn_readfirstlane(s);
+        gt_dev = (T_dev + kKV - 1) / kKV;
+        tps_dev = (a.pt + a.nb * gt_dev + a.nsplit - 1) / a.nsplit;
+    }
+#define gen_T() (POS ? T_dev : a.T)
+#define gen_gt() (POS ? gt_dev : a.gt)
+#define gen_tps() (POS ? tps_dev : a.tps)
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kTileB];      // K/V ring: 2 x 32 KiB
     const int cb = blockIdx.x, sp = blockIdx.y, bh = blockIdx.z;
     const int n = bh / a.Hkv, hk = bh - n * a.Hkv;
@@ -1571,7 +1595,7 @@ void attn_beams_kernel(BeamArgs a) {
     const int h = hk * a.G + (cvalid ? col - beam * a.G : 0);
     // the beams this column block holds (workgroup-uniform)
     const int b_lo = (cb * kDecCols) / a.G, b_hi = min(a.nb - 1, (cb * kDecCols + kDecCols - 1) / a.G);
-    const int t0 = sp * a.tps, t1 = min(a.pt + a.nb * a.gt, t0 + a.tps);
+    const int t0 = sp * gen_tps(), t1 = min(a.pt + a.nb * gen_gt(), t0 + gen_tps());
     const int64_t nslots = (int64_t)gridDim.z * a.ncb * a.nsplit;
     const int64_t slot = ((int64_t)bh * a.ncb + cb) * a.nsplit + sp;
     if (t0 >= t1) {                                            // an empty split (never with DIRECT)
@@ -1611,7 +1635,7 @@ void attn_beams_kernel(BeamArgs a) {
         const uint16_t* kb = pr ? a.k.p + n * a.k.sb + hk * a.k.sh : a.kg.p + (row0 + bt.s) * a.kg.sb + hk * a.kg.sh;
         const uint16_t* vb = pr ? a.v.p + n * a.v.sb + hk * a.v.sh : a.vg.p + (row0 + bt.s) * a.vg.sb + hk * a.vg.sh;
         const int64_t kss = pr ? a.k.ss : a.kg.ss, vss = pr ? a.v.ss : a.vg.ss;
-        const int rows = pr ? a.P : a.T;
+        const int rows = pr ? a.P : gen_T();
         const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(kb, (int64_t)(rows - 1) * kss * 2 + kRowB);
         const __amdgpu_buffer_rsrc_t rv = uniform_rsrc(vb, (int64_t)(rows - 1) * vss * 2 + kRowB);
         dma_rows(rk, kss, s, bt.g * kKV, bt.g * kKV, kKV / 4, lane);
@@ -1624,11 +1648,11 @@ void attn_beams_kernel(BeamArgs a) {
 #pragma unroll
         for (int i = 0; i < kBeamPre; ++i) {
             const int bm = b_lo + chunk * kBeamPre + i;
-            v[i] = (bt.s >= 0 && bm <= b_hi && j < a.T) ? (int)a.anc[(row0 + bm) * a.anc_ld + j] : -1;
+            v[i] = (bt.s >= 0 && bm <= b_hi && j < gen_T()) ? (int)a.anc[(row0 + bm) * a.anc_ld + j] : -1;
         }
     };
 
-    BeamTile cur = beam_tile(t0, a.pt, a.gt);
+    BeamTile cur = beam_tile(t0, a.pt, gen_gt());
     int pre[kBeamPre];
     load_anc(cur, 0, pre);
     issue(t0, cur);
@@ -1646,7 +1670,7 @@ void attn_beams_kernel(BeamArgs a) {
             w_any = w | ~in;
         } else {
             w_col = 0ull;
-            w_any = ~low_bits(a.T - cur.g * kKV);
+            w_any = ~low_bits(gen_T() - cur.g * kKV);
             for (int c = 0; b_lo + c * kBeamPre <= b_hi; ++c) {
                 if (c) load_anc(cur, c, pre);                  // more than kBeamPre beams in the block: fetched here
 #pragma unroll
@@ -1657,7 +1681,7 @@ void attn_beams_kernel(BeamArgs a) {
                 }
             }
         }
-        const BeamTile nxt = beam_next(cur, a.pt, a.gt);
+        const BeamTile nxt = beam_next(cur, a.pt, gen_gt());
         if (t + 1 < t1) {
             load_anc(nxt, 0, pre);
             issue(t + 1, nxt);
@@ -1756,6 +1780,33 @@ void attn_beams_kernel(BeamArgs a) {
         }
     }
 }
+
+// smt_attn_kv_append_pos: one step's K and V, [R][Hkv][1][128] each, into row clamp(*steps, 1, cap) - 1 of
+// the generated buffers [R][Hkv][cap][128]. One thread per 16-byte piece of a (tensor, row, head); the
+// row index is the saturated counter, so no address depends on an out-of-contract value.
+struct AppendArgs {
+    Tns kn, vn, kg, vg;
+    const int32_t* steps;
+    int Hkv, cap, n;
+};
+__global__ __launch_bounds__(256)
+void attn_kv_append_kernel(AppendArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    int s = *a.steps;
+    s = s < 1 ? 1 : (s > a.cap ? a.cap : s);
+    const int piece = i & (kD / 8 - 1), rh = i / (kD / 8);
+    const int isv = rh & 1, r_h = rh >> 1;
+    const int r = r_h / a.Hkv, h = r_h - r * a.Hkv;
+    const Tns& src = isv ? a.vn : a.kn;
+    const Tns& dst = isv ? a.vg : a.kg;
+    const u32x4_t w = *reinterpret_cast<const u32x4_t*>(src.p + r * src.sb + h * src.sh + 8 * piece);
+    *reinterpret_cast<u32x4_t*>(const_cast<uint16_t*>(dst.p) + r * dst.sb + h * dst.sh + (int64_t)(s - 1) * dst.ss + 8 * piece) = w;
+}
+
+#undef gen_T
+#undef gen_gt
+#undef gen_tps
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -2050,11 +2101,13 @@ int beam_default_splits(const smt_attn_shape* s, int32_t nb, int32_t P, int32_t 
     return n < 1 ? 1 : (int)n;
 }
 
+// smt_attn_fwd_beams (by_pos false: T is the host's) and smt_attn_fwd_beams_pos (the kernel reads *steps;
+// T is the capacity T_cap here, and the bounds, the default split count and the grid are taken on it).
 int attn_fwd_beams(const char* fn, const smt_attn_tensor* q, const smt_attn_tensor* kp, const smt_attn_tensor* vp,
                    const smt_attn_tensor* kg, const smt_attn_tensor* vg, const smt_attn_tensor* o, float* lse,
                    const uint64_t* prompt_mask, int64_t prompt_mask_ld, const uint8_t* anc, int64_t anc_ld, int32_t nb,
-                   int32_t P, int32_t P_cap, int32_t T, int32_t T_cap, int32_t num_splits, void* workspace,
-                   const smt_attn_shape* shape, hipStream_t stream) {
+                   int32_t P, int32_t P_cap, int32_t T, int32_t T_cap, const int32_t* steps, bool by_pos,
+                   int32_t num_splits, void* workspace, const smt_attn_shape* shape, hipStream_t stream) {
     int rc;
     if ((rc = check_beams(fn, shape, nb, P, T)) || (rc = check_tensor(q, "q", fn)) || (rc = check_tensor(kg, "k_gen", fn)) ||
         (rc = check_tensor(vg, "v_gen", fn)) || (rc = check_tensor(o, "o", fn)))
@@ -2065,7 +2118,9 @@ int attn_fwd_beams(const char* fn, const smt_attn_tensor* q, const smt_attn_tens
     if (!anc) return fail(-1, "%s: null anc", fn);
     if (P > P_cap) return fail(-1, "%s: P %d > P_cap %d", fn, (int)P, (int)P_cap);
     if (T > T_cap) return fail(-1, "%s: T %d > T_cap %d", fn, (int)T, (int)T_cap);
-    if (anc_ld < T) return fail(-1, "%s: anc_ld %lld < T %d", fn, (long long)anc_ld, (int)T);
+    if (by_pos && !steps) return fail(-1, "%s: null steps", fn);
+    if (by_pos && (reinterpret_cast<uintptr_t>(steps) & 3u)) return fail(-2, "%s: steps needs 4-byte alignment (int32)", fn);
+    if (anc_ld < T) return fail(-1, "%s: anc_ld %lld < %s %d", fn, (long long)anc_ld, by_pos ? "T_cap" : "T", (int)T);
     if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
     if ((rc = check_kmask_ld(fn, prompt_mask, prompt_mask_ld, P, "P"))) return rc;
     const int nsplit = num_splits ? num_splits : beam_default_splits(shape, nb, P, T);
@@ -2098,9 +2153,14 @@ int attn_fwd_beams(const char* fn, const smt_attn_tensor* q, const smt_attn_tens
     a.tps = (beam_tiles(nb, P, T) + nsplit - 1) / nsplit;
     a.sl2 = shape->scale * 1.4426950408889634f;
     const dim3 grid((unsigned)a.ncb, (unsigned)nsplit, (unsigned)bh);
-    dispatch(shape->dtype, [&](auto f, auto km, auto direct) {
-        hipLaunchKernelGGL((attn_beams_kernel<km(), f(), direct()>), grid, dim3(64), 0, stream, a);
-    }, a.kmask != nullptr, nsplit == 1);
+    BeamPosArgs ap;                                        // the device-counter form of the same call
+    static_cast<BeamArgs&>(ap) = a;
+    ap.steps = steps;
+    dispatch(shape->dtype, [&](auto f, auto km, auto direct, auto pos_form) {
+        if constexpr (pos_form())
+            hipLaunchKernelGGL((attn_beams_kernel<km(), f(), direct(), BeamPosArgs>), grid, dim3(64), 0, stream, ap);
+        else hipLaunchKernelGGL((attn_beams_kernel<km(), f(), direct(), BeamArgs>), grid, dim3(64), 0, stream, a);
+    }, a.kmask != nullptr, nsplit == 1, by_pos);
     if ((rc = check_launch("attn_beams_kernel")) || nsplit == 1) return rc;
     const dim3 cgrid((unsigned)a.ncols, (unsigned)bh);
     dispatch(shape->dtype, [&](auto f) {
@@ -2296,7 +2356,40 @@ int smt_attn_fwd_beams(const smt_attn_tensor* q, const smt_attn_tensor* k_prompt
                        int32_t nb, int32_t P, int32_t P_cap, int32_t T, int32_t T_cap, int32_t num_splits,
                        void* workspace, const smt_attn_shape* shape, hipStream_t stream) {
     return attn_fwd_beams("smt_attn_fwd_beams", q, k_prompt, v_prompt, k_gen, v_gen, o, lse, prompt_mask, prompt_mask_ld,
-                          anc, anc_ld, nb, P, P_cap, T, T_cap, num_splits, workspace, shape, stream);
+                          anc, anc_ld, nb, P, P_cap, T, T_cap, nullptr, false, num_splits, workspace, shape, stream);
+}
+
+int smt_attn_fwd_beams_pos(const smt_attn_tensor* q, const smt_attn_tensor* k_prompt, const smt_attn_tensor* v_prompt,
+                           const smt_attn_tensor* k_gen, const smt_attn_tensor* v_gen, const smt_attn_tensor* o, float* lse,
+                           const uint64_t* prompt_mask, int64_t prompt_mask_ld, const uint8_t* anc, int64_t anc_ld,
+                           int32_t nb, int32_t P, int32_t P_cap, const int32_t* steps, int32_t T_cap, int32_t num_splits,
+                           void* workspace, const smt_attn_shape* shape, hipStream_t stream) {
+    return attn_fwd_beams("smt_attn_fwd_beams_pos", q, k_prompt, v_prompt, k_gen, v_gen, o, lse, prompt_mask,
+                          prompt_mask_ld, anc, anc_ld, nb, P, P_cap, T_cap, T_cap, steps, true, num_splits, workspace, shape,
+                          stream);
+}
+
+int smt_attn_kv_append_pos(const smt_attn_tensor* k_new, const smt_attn_tensor* v_new, const smt_attn_tensor* k_gen,
+                           const smt_attn_tensor* v_gen, const int32_t* steps, int32_t rows, int32_t Hkv, int32_t T_cap,
+                           int32_t dtype, hipStream_t stream) {
+    const char* fn = "smt_attn_kv_append_pos";
+    int rc;
+    if ((rc = check_tensor(k_new, "k_new", fn)) || (rc = check_tensor(v_new, "v_new", fn)) ||
+        (rc = check_tensor(k_gen, "k_gen", fn)) || (rc = check_tensor(v_gen, "v_gen", fn)))
+        return rc;
+    if (!steps) return fail(-1, "%s: null steps", fn);
+    if (reinterpret_cast<uintptr_t>(steps) & 3u) return fail(-2, "%s: steps needs 4-byte alignment (int32)", fn);
+    if (dtype != SMT_DTYPE_BF16 && dtype != SMT_DTYPE_FP16)
+        return fail(-1, "%s: dtype %d is not a 16-bit format (SMT_DTYPE_BF16 / SMT_DTYPE_FP16)", fn, (int)dtype);
+    if (rows < 1 || Hkv < 1 || T_cap < 1)
+        return fail(-1, "%s: rows = %d, Hkv = %d, T_cap = %d (each at least 1)", fn, (int)rows, (int)Hkv, (int)T_cap);
+    const int64_t n = (int64_t)rows * Hkv * 2 * (kD / 8);      // one 16-byte piece per thread
+    if (n > 0x7fffffffLL) return fail(-1, "%s: rows * Hkv = %lld is too large", fn, (long long)rows * Hkv);
+    AppendArgs a;
+    a.kn = tns(k_new); a.vn = tns(v_new); a.kg = tns(k_gen); a.vg = tns(v_gen);
+    a.steps = steps; a.Hkv = Hkv; a.cap = T_cap; a.n = (int)n;
+    hipLaunchKernelGGL(attn_kv_append_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+    return check_launch("attn_kv_append_kernel");
 }
 
 }  // extern "C"

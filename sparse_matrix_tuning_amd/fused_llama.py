@@ -1147,15 +1147,27 @@ def flash_attention_beams(q, k_prompt, v_prompt, k_gen, v_gen, ancestors, num_be
     ``prompt_len`` / ``gen_len`` are never read, and no address depends on a value in ``ancestors`` (a
     value >= nb matches nothing; a row that sees no key at all gets zeros and lse = +inf).
     ``num_splits``, ``return_lse`` (fp32 ``[N * nb, Hq]``, log2 units): as in
-    :func:`flash_attention_cached`. ``prompt_len`` and ``gen_len`` are host integers; nothing
-    synchronises with the host. There is no backward: an input that requires grad while gradients are
-    enabled raises."""
+    :func:`flash_attention_cached`. ``prompt_len`` is a host integer; nothing synchronises with the
+    host. ``gen_len`` is a host integer, or a one-element int32 tensor on q's device: the kernel reads
+    it (``smt_attn_fwd_beams_pos``), the host never does, so the call can be captured in a graph and
+    replayed while the counter, the buffers and ``ancestors`` change in place. The kernel saturates
+    the counter into ``[1, T_cap]``; ``ancestors`` is then ``[N * nb, >= T_cap]``, and the split count
+    and the workspace follow the capacity. For a given ``num_splits`` the result equals the integer
+    call's with ``gen_len = clamp(counter, 1, T_cap)`` bit for bit. There is no backward: an input that
+    requires grad while gradients are enabled raises."""
     tensors = (q, k_prompt, v_prompt, k_gen, v_gen)
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise NotImplementedError("flash_attention_beams: beam-shared attention has no backward (inference only); run "
                                   "under torch.no_grad() or detach the inputs")
     for t, n in zip(tensors, ("q", "k_prompt", "v_prompt", "k_gen", "v_gen")):
         _need(t, "beam-shared flash attention " + n, like=q)
+    steps = None
+    if isinstance(gen_len, torch.Tensor):
+        steps = gen_len
+        if steps.device != q.device or steps.dtype != torch.int32 or steps.numel() != 1:
+            raise ValueError(f"beam-shared flash attention: a tensor gen_len is one int32 element on {q.device} (got "
+                             f"{steps.dtype} {tuple(steps.shape)} on {steps.device})")
+        gen_len = k_gen.shape[2] if k_gen.dim() == 4 else 0     # the host's arithmetic runs on the capacity
     nb, P, T = int(num_beams), int(prompt_len), int(gen_len)
     if any(t.dim() != 4 for t in tensors) or v_prompt.shape != k_prompt.shape or v_gen.shape != k_gen.shape:
         raise NotImplementedError("beam-shared flash attention: 4-D q, k_prompt / v_prompt and k_gen / v_gen of equal "
@@ -1205,24 +1217,68 @@ def flash_attention_beams(q, k_prompt, v_prompt, k_gen, v_gen, ancestors, num_be
     ws_bytes = lib.smt_attn_beams_workspace(ctypes.byref(shape), nb, P, T, num_splits)
     _hip._check(min(ws_bytes, 0), "smt_attn_beams_workspace")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes else None
+    fn = "smt_attn_fwd_beams" if steps is None else "smt_attn_fwd_beams_pos"
     with torch.cuda.device(q.device):
-        rc = lib.smt_attn_fwd_beams(_attn_ref(q), _attn_ref(k_prompt), _attn_ref(v_prompt), _attn_ref(k_gen),
-                                    _attn_ref(v_gen), _attn_ref(o.transpose(1, 2)), _hip._ptr(lse), pm, pm_ld,
-                                    anc.data_ptr(), anc.stride(0) if R > 1 else anc.shape[1], nb, P, P_cap, T, T_cap,
-                                    num_splits, _hip._ptr(ws), ctypes.byref(shape), _stream(q))
-    _hip._check(rc, "smt_attn_fwd_beams")
+        rc = getattr(lib, fn)(_attn_ref(q), _attn_ref(k_prompt), _attn_ref(v_prompt), _attn_ref(k_gen),
+                              _attn_ref(v_gen), _attn_ref(o.transpose(1, 2)), _hip._ptr(lse), pm, pm_ld,
+                              anc.data_ptr(), anc.stride(0) if R > 1 else anc.shape[1], nb, P, P_cap,
+                              T if steps is None else steps.data_ptr(), T_cap,
+                              num_splits, _hip._ptr(ws), ctypes.byref(shape), _stream(q))
+    _hip._check(rc, fn)
     return (o, lse) if return_lse else o
+
+
+def kv_append(k_new, v_new, k_gen, v_gen, steps) -> None:
+    """One decode step's K / V into the generated buffers of a beam-shared cache
+    (``smt_attn_kv_append_pos``): k_new / v_new ``[R, Hkv, 1, 128]`` (any strides with head_dim
+    innermost: the model hands over a transposed view) go into row ``clamp(steps, 1, T_cap) - 1`` of
+    k_gen / v_gen ``[R, Hkv, T_cap, 128]``, in one launch. ``steps``: the one-element int32 counter on
+    the buffers' device that :func:`flash_attention_beams` takes as ``gen_len``; the kernel reads it,
+    the host never does, and no value of it can send the write outside the buffers."""
+    for t, n in ((k_new, "k_new"), (v_new, "v_new"), (k_gen, "k_gen"), (v_gen, "v_gen")):
+        _need(t, "kv_append " + n, like=k_gen)
+    if k_gen.dim() != 4 or v_gen.shape != k_gen.shape or k_gen.shape[3] != 128:
+        raise NotImplementedError(f"kv_append: k_gen / v_gen [R, Hkv, T_cap, 128] (got {tuple(k_gen.shape)}, "
+                                  f"{tuple(v_gen.shape)})")
+    R, Hkv, T_cap, D = k_gen.shape
+    if k_new.shape != (R, Hkv, 1, D) or v_new.shape != (R, Hkv, 1, D):
+        raise ValueError(f"kv_append: k_new / v_new must be [{R}, {Hkv}, 1, {D}] (got {tuple(k_new.shape)}, "
+                         f"{tuple(v_new.shape)})")
+    if (not isinstance(steps, torch.Tensor) or steps.device != k_gen.device or steps.dtype != torch.int32
+            or steps.numel() != 1):
+        raise ValueError(f"kv_append: steps is one int32 element on {k_gen.device}")
+    if not (k_gen.stride(3) == 1 and v_gen.stride(3) == 1 and _attn_ready(k_gen) is k_gen and _attn_ready(v_gen) is v_gen):
+        raise ValueError("kv_append: k_gen / v_gen need head_dim innermost and 16-byte aligned rows (they are written in place)")
+    new = []
+    for t in (k_new, v_new):
+        # the stride of a one-element dimension carries no meaning: drop it before the alignment test
+        t = t.as_strided(t.shape, (t.stride(0), t.stride(1), 0, t.stride(3)))
+        new.append(_attn_ready(t))
+    with torch.cuda.device(k_gen.device):
+        rc = _hip.load().smt_attn_kv_append_pos(_attn_ref(new[0]), _attn_ref(new[1]), _attn_ref(k_gen), _attn_ref(v_gen),
+                                                steps.data_ptr(), R, Hkv, T_cap, _dt(k_gen), _stream(k_gen))
+    _hip._check(rc, "smt_attn_kv_append_pos")
 
 
 def _beam_decode(layer, query, attention_mask, scaling):
     """A decode step on a :class:`~sparse_matrix_tuning_amd.beam_cache.BeamSharedCache`: ``layer`` is the
     cache layer that tagged the K / V its ``update`` returned. The prompt's key mask is the
     :class:`CacheMask`'s, rows ``[::nb]`` and the words of the first ``prompt_len`` keys (a view: the
-    beams of a sample share their padding); the columns of generated positions are not consulted."""
+    beams of a sample share their padding); the columns of generated positions are not consulted.
+    A ``device_steps`` cache builds those words once, at its first decode step, and keeps them in its
+    state (a copy: the mask ``generate()`` grows is then no input of a later step), and hands the
+    kernel its device counter in place of ``layer.steps`` (``smt_attn_fwd_beams_pos``)."""
     if attention_mask is not None and not isinstance(attention_mask, CacheMask):
         raise NotImplementedError("smt_flash attention: a decode step on a BeamSharedCache takes the CacheMask "
                                   f"smt_flash_mask builds (got {type(attention_mask).__name__})")
-    nb, P = layer.state.num_beams, layer.prompt_len
+    st = layer.state
+    nb, P = st.num_beams, layer.prompt_len
+    if st.device_steps:
+        if st.prompt_mask is None:
+            km = attention_mask.key_mask if attention_mask is not None else None
+            st.prompt_mask = (KeyMask(km.bits[::nb, :-(-P // 64)].clone(), P) if km is not None and P else None,)
+        return flash_attention_beams(query, layer.k_prompt, layer.v_prompt, layer.k_gen, layer.v_gen, st.anc, nb, P,
+                                     st.counter, prompt_key_mask=st.prompt_mask[0], scale=scaling)
     km = attention_mask.key_mask if attention_mask is not None else None
     pm = KeyMask(km.bits[::nb, :-(-P // 64)], P) if km is not None else None
     return flash_attention_beams(query, layer.k_prompt, layer.v_prompt, layer.k_gen, layer.v_gen, layer.state.anc, nb, P,
@@ -1433,6 +1489,119 @@ def eager_apply_rotary_pos_emb(*a, **k):
     return _ml() and _EAGER["rope"](*a, **k)
 
 
+class DecodeGraph:
+    """The decode runner of one ``BeamSharedCache(graph=True)``, hence of one ``generate()`` call: the
+    first decode step runs eagerly (the warm-up: allocator, code objects, the GEMM library's choices,
+    and the cache's prompt mask words), the second is captured with ``torch.cuda.graph`` (one stream, a
+    private pool; the forward is a linear chain), the later ones replay it. What changes from step to
+    step reaches the graph through fixed buffers (``input_ids``, ``position_ids``, ``cache_position``
+    where the caller passes one) and through device memory the kernels read themselves: the cache's
+    counter, its buffers and its ancestry table. The growing 2-D ``attention_mask`` is no input. A
+    capture that raises, raises: nothing falls back."""
+
+    _DYNAMIC_ROPE = ("dynamic", "longrope")              # their tables follow the running length (a host read per step)
+
+    def __init__(self, cache):
+        self.cache = cache
+        self.decodes = 0
+        self.graph = self.static = self.logits = self.keys = None
+
+    @staticmethod
+    def _rope_types(model):
+        found = []
+        rot = getattr(getattr(model, "model", None), "rotary_emb", None)
+        found.append(getattr(rot, "rope_type", None))
+        for name in ("rope_parameters", "rope_scaling"):
+            par = getattr(model.config, name, None)
+            if isinstance(par, dict):
+                found += [par.get("rope_type"), par.get("type")]
+        return [t for t in found if isinstance(t, str)]
+
+    def warm_up(self, model) -> None:
+        """Before the first decode step, which the caller runs eagerly."""
+        bad = [t for t in self._rope_types(model) if t in self._DYNAMIC_ROPE]
+        if bad:
+            raise NotImplementedError(f"BeamSharedCache(graph=True): rope_type {bad[0]!r} recomputes its tables from "
+                                      "the running length at every step; a captured decode step cannot follow it "
+                                      "(use graph=False)")
+        self.decodes = 1
+
+    def step(self, forward, input_ids, position_ids, tensors: dict, passthrough: dict):
+        """A decode step after the warm-up. ``forward(**kw)``: the model's eager forward; ``tensors``:
+        further per-step tensor inputs (``cache_position``) by name; ``passthrough``: what is the same
+        at every step."""
+        cache = self.cache
+        self.decodes += 1
+        if cache.layers[0].steps >= cache.state.capacity:
+            raise RuntimeError(f"BeamSharedCache: max_new_tokens = {cache.state.capacity} generated positions are full")
+        host_pos = position_ids is None                  # the model's own: arange(1) + the cache's length
+        if host_pos:
+            position_ids = torch.full((1, 1), cache.get_seq_length(), dtype=torch.int64, device=input_ids.device)
+        inputs = dict(tensors, input_ids=input_ids, position_ids=position_ids)
+        # what the captured step was called with, the tensors' values apart
+        keys = (host_pos, tuple(sorted((k, v.shape, v.dtype) for k, v in inputs.items())),
+                tuple(sorted((k, repr(v)) for k, v in passthrough.items())))
+        if self.graph is None:
+            self.static, self.keys = {k: v.clone() for k, v in inputs.items()}, keys
+            steps = [ly.steps for ly in cache.layers]
+            torch.cuda.synchronize(input_ids.device)
+            graph = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(graph):
+                    out = forward(**self.static, attention_mask=None, past_key_values=cache, **passthrough)
+            except BaseException:
+                for ly, n in zip(cache.layers, steps):   # the capture launched nothing: the host count goes back
+                    ly.steps = n
+                raise
+            self.graph, self.logits = graph, out.logits
+            cache.graph_captures += 1
+            graph.replay()                               # capturing ran nothing: this is the step itself
+        else:
+            if keys != self.keys:
+                raise RuntimeError("BeamSharedCache(graph=True): this decode step's arguments differ from the captured "
+                                   f"step's ({keys} vs {self.keys}); one cache serves one generate() call")
+            for k, v in inputs.items():
+                self.static[k].copy_(v)
+            self.graph.replay()
+            for ly in cache.layers:                      # what update() counts on the host
+                ly.steps += 1
+            cache.graph_replays += 1
+        from transformers.modeling_outputs import CausalLMOutputWithPast
+        return CausalLMOutputWithPast(loss=None, logits=self.logits.clone(), past_key_values=cache)
+
+
+def smt_causal_lm_forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
+                          inputs_embeds=None, labels=None, use_cache=None, logits_to_keep=0, **kwargs):
+    """The model-level forward ``patch_llama(attention=True)`` installs. A graphed decode step (gradients
+    off, ``past_key_values`` a ``BeamSharedCache(graph=True)`` past its prefill, ``input_ids`` ``[R, 1]``,
+    no labels, ``inputs_embeds``, hidden-state / attention outputs or ``return_dict=False``) goes to the
+    cache's :class:`DecodeGraph`; every other call passes through unchanged to what ran before:
+    :func:`fused_causal_lm_forward` where the fused LM-head loss is on, else transformers' forward."""
+    from .beam_cache import BeamSharedCache
+    prev = fused_causal_lm_forward if self.__dict__.get("_smt_lm_head_forward") else type(self).forward
+    eager = lambda **kw: prev(self, **kw)
+    cache = past_key_values
+    if (isinstance(cache, BeamSharedCache) and cache.graph and not torch.is_grad_enabled()
+            and cache.layers[0].is_initialized and isinstance(input_ids, torch.Tensor) and input_ids.dim() == 2
+            and input_ids.shape[1] == 1 and input_ids.is_cuda and labels is None and inputs_embeds is None
+            and kwargs.get("return_dict") is not False and not kwargs.get("output_hidden_states")
+            and not kwargs.get("output_attentions")
+            and not any(isinstance(v, torch.Tensor) for k, v in kwargs.items() if k != "cache_position")):
+        if cache.decode_runner is None:
+            cache.decode_runner = DecodeGraph(cache)
+        runner = cache.decode_runner
+        tensors = {k: kwargs.pop(k) for k in ("cache_position",) if isinstance(kwargs.get(k), torch.Tensor)}
+        passthrough = dict(kwargs, use_cache=use_cache, logits_to_keep=logits_to_keep)
+        if runner.decodes == 0:                          # the warm-up step: eager, with the mask as it came
+            runner.warm_up(self)
+            return eager(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
+                         past_key_values=cache, use_cache=use_cache, logits_to_keep=logits_to_keep, **tensors, **kwargs)
+        return runner.step(eager, input_ids, position_ids, tensors, passthrough)
+    return eager(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
+                 past_key_values=past_key_values, inputs_embeds=inputs_embeds, labels=labels, use_cache=use_cache,
+                 logits_to_keep=logits_to_keep, **kwargs)
+
+
 def _keep_2d_mask(config=None, inputs_embeds=None, attention_mask=None, **kwargs):
     """``create_masks_for_generate`` of a patched model: the 2-D padding mask as it came."""
     return attention_mask
@@ -1446,6 +1615,9 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
     ``smt_flash``; the loss through the model's ``loss_function`` attribute. ``lm_head_loss``
     (default: ``SMT_LM_HEAD_LOSS``, on): with ``loss``, the model's forward runs the LM head and the
     loss together, chunk by chunk, without the full logits (:func:`fused_causal_lm_forward`).
+    With ``attention``, a ``LlamaForCausalLM`` also gets :func:`smt_causal_lm_forward`, which replays the
+    decode steps of a ``BeamSharedCache(graph=True)`` from a captured graph and passes every other call
+    through unchanged (to :func:`fused_causal_lm_forward` where that is on, else to transformers').
     With ``attention``, ``generation_config.disable_compile`` is set and the model keeps the 2-D mask
     in ``generate()`` (``create_masks_for_generate``), so that ``cache_implementation="static"`` runs
     the kernels eagerly; :func:`unpatch_llama` restores both.
@@ -1474,6 +1646,11 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
         if gen is not None and "_smt_prev_disable_compile" not in model.__dict__:
             model.__dict__["_smt_prev_disable_compile"] = getattr(gen, "disable_compile", False)
             gen.disable_compile = True
+        if isinstance(model, ml.LlamaForCausalLM):
+            # the model-level forward that hands the decode steps of a BeamSharedCache(graph=True) to the
+            # cache's DecodeGraph; every other call passes through to what ran before
+            model.__dict__["_smt_lm_head_forward"] = bool(counts["lm_head_loss"])
+            model.forward = smt_causal_lm_forward.__get__(model, type(model))
         if gen is not None:
             # ... and, for a compilable cache, builds the mask before the forward and passes the
             # result in place of the 2-D mask; only a 4-D tensor survives that. Keep the 2-D mask:
@@ -1518,6 +1695,7 @@ def unpatch_llama(model: nn.Module = None) -> None:
             del model.__dict__["_loss_function"]
         if "forward" in model.__dict__:
             del model.__dict__["forward"]
+        model.__dict__.pop("_smt_lm_head_forward", None)
         for m in model.modules():
             if isinstance(m, (ml.LlamaRMSNorm, ml.LlamaMLP, ml.LlamaDecoderLayer)) and "forward" in m.__dict__:
                 del m.__dict__["forward"]
