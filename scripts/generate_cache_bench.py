@@ -13,7 +13,13 @@ leg's lines also carry ``capture_ms``, the wall time of the capture (torch.cuda.
 decode forward, the step's own first replay included) measured around it between synchronisations, and
 the cache's ``graph_captures`` / ``graph_replays``; its ``seconds`` include the capture. One
 ``"cache": "ratio"`` line per (size, round) divides the ``beam_shared`` leg by the graph leg. The first
-three legs are bound by the host (a decode step is about 500 launches at 32 layers)."""
+three legs are bound by the host (a decode step is about 500 launches at 32 layers).
+
+``--loop transformers smt`` adds the decoding loop as an axis: transformers' ``_beam_search`` and
+``custom_generate=smt_beam_search`` (sparse_matrix_tuning_amd/beam_search.py: the scoring of a token as one
+smt_beam_topk call). The (cache, loop) legs alternate within a round; every line carries ``loop``, and the
+smt legs ``same_tokens_as_transformers_loop`` (the same cache under transformers' loop) and the loop's
+``delegated`` count. ``--repetition-penalty 1.1`` is the reference's setting; ``--caches`` picks the legs."""
 import argparse
 import json
 import os
@@ -24,6 +30,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import MODELS, build_model  # noqa: E402
+from sparse_matrix_tuning_amd import beam_search  # noqa: E402
 from sparse_matrix_tuning_amd.beam_cache import BeamSharedCache  # noqa: E402
 from sparse_matrix_tuning_amd.fused_llama import DecodeGraph, patch_llama  # noqa: E402
 
@@ -36,6 +43,10 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=256)
     ap.add_argument("--new", type=int, nargs="+", default=[64])
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--loop", nargs="+", default=["transformers"], choices=["transformers", "smt"])
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--caches", nargs="+", default=["dynamic", "static", "beam_shared", "beam_shared_graph"],
+                    choices=["dynamic", "static", "beam_shared", "beam_shared_graph"])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("generate_cache_bench: needs the GPU")
@@ -66,12 +77,19 @@ def main():
     DecodeGraph.step = timed_step
 
     for new in a.new:
-        kinds = (("dynamic", lambda: {}), ("static", lambda: {"cache_implementation": "static"}),
-                 ("beam_shared", lambda: {"past_key_values": BeamSharedCache(model.config, a.beams, new)}),
-                 ("beam_shared_graph", lambda: {"past_key_values": BeamSharedCache(model.config, a.beams, new, graph=True)}))
+        caches = {"dynamic": lambda: {}, "static": lambda: {"cache_implementation": "static"},
+                  "beam_shared": lambda: {"past_key_values": BeamSharedCache(model.config, a.beams, new)},
+                  "beam_shared_graph": lambda: {"past_key_values": BeamSharedCache(model.config, a.beams, new, graph=True)}}
+        extra = {} if a.repetition_penalty == 1.0 else {"repetition_penalty": a.repetition_penalty}
+        loops = {"transformers": {}, "smt": {"custom_generate": beam_search.smt_beam_search}}
+        leg = lambda cache, loop: cache if loop == "transformers" else f"{cache}+{loop}"
+        kinds = tuple((leg(c, lp), (lambda c=c, lp=lp: {**caches[c](), **loops[lp], **extra}))
+                      for c in a.caches for lp in a.loop)
+        first = kinds[0][0]
 
         def run(kw):
             kw = kw()
+            beam_search.stats.reset()
             torch.cuda.synchronize()
             t = time.perf_counter()
             with torch.no_grad():
@@ -81,26 +99,38 @@ def main():
             return time.perf_counter() - t, out, kw.get("past_key_values")
 
         outs = {name: run(kw)[1] for name, kw in kinds}    # untimed
-        same = {name: bool(torch.equal(outs["dynamic"], o)) for name, o in outs.items()}
-        same_graph = bool(torch.equal(outs["beam_shared"], outs["beam_shared_graph"]))
+        same = {name: bool(torch.equal(outs[first], o)) for name, o in outs.items()}
+        same_graph = ("beam_shared" in outs and "beam_shared_graph" in outs
+                      and bool(torch.equal(outs["beam_shared"], outs["beam_shared_graph"])))
         for rnd in range(a.rounds):
             secs = {}
             for name, kw in kinds:
                 s, out, cache = run(kw)
                 secs[name] = s
-                line = {"cache": name, "round": rnd, "model": a.model, "prompts": a.prompts, "beams": a.beams,
+                line = {"cache": name.split("+")[0], "loop": "smt" if name.endswith("+smt") else "transformers",
+                        "repetition_penalty": a.repetition_penalty,
+                        "round": rnd, "model": a.model, "prompts": a.prompts, "beams": a.beams,
                         "prompt_len": a.prompt_len, "new_tokens": new, "seconds": round(s, 4),
                         "ms_per_token": round(1e3 * s / new, 3), "shape": list(out.shape),
-                        "same_tokens_as_dynamic": same[name]}
-                if name == "beam_shared_graph":
+                        f"same_tokens_as_{first}": same[name]}
+                if name.endswith("+smt"):
+                    line.update(delegated=beam_search.stats.delegated)
+                    if name.split("+")[0] in outs:
+                        line.update(same_tokens_as_transformers_loop=bool(torch.equal(outs[name.split("+")[0]], outs[name])))
+                if name.startswith("beam_shared_graph"):
                     line.update(capture_ms=round(capture["ms"], 2), graph_captures=cache.graph_captures,
                                 graph_replays=cache.graph_replays, same_tokens_as_beam_shared=same_graph,
                                 ms_per_token_without_capture=round((1e3 * s - capture["ms"]) / new, 3))
                 print(json.dumps(line), flush=True)
-            print(json.dumps({"cache": "ratio", "round": rnd, "new_tokens": new,
-                              "seconds_beam_shared_over_graph": round(secs["beam_shared"] / secs["beam_shared_graph"], 3),
-                              "seconds_dynamic_over_graph": round(secs["dynamic"] / secs["beam_shared_graph"], 3)}),
-                  flush=True)
+            ratio = {"cache": "ratio", "round": rnd, "new_tokens": new}
+            if "beam_shared_graph" in secs:
+                for other in ("beam_shared", "dynamic"):
+                    if other in secs:
+                        ratio[f"seconds_{other}_over_graph"] = round(secs[other] / secs["beam_shared_graph"], 3)
+            for c in a.caches:
+                if c in secs and c + "+smt" in secs:
+                    ratio[f"seconds_{c}_transformers_over_smt"] = round(secs[c] / secs[c + "+smt"], 3)
+            print(json.dumps(ratio), flush=True)
 
 
 if __name__ == "__main__":

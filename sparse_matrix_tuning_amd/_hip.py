@@ -27,7 +27,7 @@ _DT = {torch.bfloat16: DTYPE_BF16, torch.float32: DTYPE_FP32, torch.float16: DTY
 ABI_VERSION = 13            # include/smt_hip.h: 16-bit dtype of the model ops / attention (v13),
                             # smt_adamw_args.param_dtype (v12), smt_wgrad_module.operand_dtype (v11)
 
-# Every function the headers declare (include/smt_hip.h, smt_model_ops.h, smt_attention.h); tests check the
+# Every function the headers declare (include/smt_hip.h, smt_model_ops.h, smt_attention.h, smt_fp8.h, smt_beam.h); tests check the
 # library exports each of them.
 ABI_FUNCTIONS = (
     "smt_last_error", "smt_abi_version", "smt_wgrad_workspace_bytes", "smt_tile_wgrad", "smt_wgrad_batch_workspace_bytes",
@@ -52,6 +52,7 @@ ABI_FUNCTIONS = (
     "smt_swiglu_fwd_quant_e4m3", "smt_swiglu_bwd_quant_e4m3", "smt_swiglu_bwd_quant_e4m3_packed",
     "smt_rmsnorm_fwd_quant_e4m3",
     "smt_rmsnorm_bwd_add_quant_e4m3",
+    "smt_beam_last_error", "smt_beam_topk_workspace", "smt_beam_topk",
 )
 
 
@@ -221,6 +222,10 @@ _SIGS = {
     "smt_swiglu_bwd_quant_e4m3": (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _I64, _P, _P, _P, _P]),
     "smt_swiglu_bwd_quant_e4m3_packed": (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _I64, _P, _P, _P, _I64, _P, _P,
                                                          _I64, _P]),
+    "smt_beam_last_error": (ctypes.c_char_p, []),
+    "smt_beam_topk_workspace": (_I64, [_I32, _I32, _I64, _I32]),
+    "smt_beam_topk": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I64, _P, _P, _I64, _I32, ctypes.c_float, _P, _I32, _I32,
+                                     _P, _P, _P, _P]),
 }
 
 
@@ -275,6 +280,8 @@ def _check(rc: int, what: str) -> None:
             err = lib.smt_model_ops_last_error           # llama_kernels.hip (incl. smt_rmsnorm_fwd_quant_e4m3)
         elif what.startswith("smt_attn"):
             err = lib.smt_attn_last_error
+        elif what.startswith("smt_beam"):
+            err = lib.smt_beam_last_error              # beam_kernels.hip
         else:
             err = lib.smt_last_error
         raise RuntimeError(f"{what} failed (status {rc}): {err().decode(errors='replace')}")

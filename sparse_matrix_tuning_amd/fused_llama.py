@@ -27,6 +27,7 @@ chain rounds to the model's dtype (tests/test_gpu_fused_fp16.py). fp32 models an
 from __future__ import annotations
 
 import ctypes
+import gc
 import os
 import weakref
 
@@ -1502,9 +1503,15 @@ class DecodeGraph:
     _DYNAMIC_ROPE = ("dynamic", "longrope")              # their tables follow the running length (a host read per step)
 
     def __init__(self, cache):
-        self.cache = cache
+        # the cache owns its runner; a weak reference back, so that the pair is no reference cycle and a
+        # dropped cache frees its graph and its private pool at once, not at some later collection
+        self._cache = weakref.ref(cache)
         self.decodes = 0
         self.graph = self.static = self.logits = self.keys = None
+
+    @property
+    def cache(self):
+        return self._cache()
 
     @staticmethod
     def _rope_types(model):
@@ -1546,6 +1553,13 @@ class DecodeGraph:
             steps = [ly.steps for ly in cache.layers]
             torch.cuda.synchronize(input_ids.device)
             graph = torch.cuda.CUDAGraph()
+            # No garbage collection inside the capture: torch.cuda.graph no longer collects before it
+            # begins, and a dead cycle that holds device memory or another graph (an earlier call's
+            # objects) would be freed in the middle of the captured forward, which aborts the process.
+            # Collect now, then keep the collector off until the capture has ended.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
             try:
                 with torch.cuda.graph(graph):
                     out = forward(**self.static, attention_mask=None, past_key_values=cache, **passthrough)
@@ -1553,6 +1567,9 @@ class DecodeGraph:
                 for ly, n in zip(cache.layers, steps):   # the capture launched nothing: the host count goes back
                     ly.steps = n
                 raise
+            finally:
+                if gc_was_on:
+                    gc.enable()
             self.graph, self.logits = graph, out.logits
             cache.graph_captures += 1
             graph.replay()                               # capturing ran nothing: this is the step itself
