@@ -14,16 +14,22 @@ folded into the plain templates as a fourth parameter ``DOC``:
 symbol, its instruction lines with basic-block labels and comments stripped (labels are renumbered
 between builds). ``diff`` pairs kernels by demangled name after applying ``--map`` substitutions
 (a template parameter added with its old value, e.g. ``--map "<4, false>=<4, false, 0>"``) and prints
-identical / differing / unmatched kernels. Exit status 1 when any paired kernel differs."""
+identical / differing / unmatched kernels; for a differing kernel also the per-mnemonic count deltas and
+its register, scratch and LDS figures (the assembly metadata's, kept by ``dump``) before and after. Exit
+status 1 when any paired kernel differs."""
 import json
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from collections import Counter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+
+
+META = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
 def dump(src, out):
@@ -51,14 +57,26 @@ def dump(src, out):
         if not ins or ins.startswith(".") or re.match(r"^\.?L\w+:", ins):
             continue
         kernels[cur].append(re.sub(r"\.LBB\d+_\d+", ".LBB", ins))
+    # the metadata's per-kernel resource figures: 4-space "key: value" lines of the block that holds .name
+    meta, block = {}, {}
+    for line in text[text.find("amdhsa.kernels:"):].splitlines()[1:]:
+        if line.startswith("  - ") or not line.startswith(" "):
+            meta[block.get(".name")] = {k: int(block[k]) for k in META if k in block}
+            block = {}
+            if not line.startswith(" "):
+                break
+        m = re.match(r"^(?:  - |    )(\.\w+):\s*(\S+)\s*$", line)
+        if m:
+            block[m.group(1)] = m.group(2)
     names = subprocess.run(["c++filt"], input="\n".join(kernels), capture_output=True, text=True).stdout.split("\n")
-    res = {dm: kernels[k] for k, dm in zip(kernels, names) if kernels[k] and "(" in dm}
+    res = {dm: {"ins": kernels[k], "meta": meta.get(k, {})} for k, dm in zip(kernels, names) if kernels[k] and "(" in dm}
     json.dump(res, open(out, "w"))
     print(f"{len(res)} kernels -> {out}")
 
 
 def diff(a, b, maps):
-    A, B = json.load(open(a)), json.load(open(b))
+    # a dump from before the metadata was kept is a bare instruction list per kernel
+    A, B = ({n: v if isinstance(v, dict) else {"ins": v, "meta": {}} for n, v in json.load(open(f)).items()} for f in (a, b))
     sub = [(m[0], m[1].split("=", 1)) for m in maps]
 
     def key(n):
@@ -70,14 +88,17 @@ def diff(a, b, maps):
     for n, v in Am.items():
         if n not in B:
             missing.append(n)
-        elif B[n] == v:
+        elif B[n]["ins"] == v["ins"]:
             same.append(n)
         else:
             differ.append(n)
     for n in same:
         print("identical ", n)
     for n in differ:
-        print("DIFFERENT ", n, len(Am[n]), len(B[n]))
+        print("DIFFERENT ", n, len(Am[n]["ins"]), len(B[n]["ins"]))
+        ca, cb = (Counter(i.split()[0] for i in k[n]["ins"]) for k in (Am, B))
+        print("    counts:", " ".join(f"{m} {cb[m] - ca[m]:+d}" for m in sorted(ca | cb) if ca[m] != cb[m]) or "equal")
+        print("    meta:  ", " ".join(f"{k} {Am[n]['meta'].get(k)} -> {B[n]['meta'].get(k)}" for k in META))
     for n in missing:
         print("unmatched ", n)
     print(f"{len(same)} identical, {len(differ)} different, {len(missing)} unmatched of {len(Am)} before; "

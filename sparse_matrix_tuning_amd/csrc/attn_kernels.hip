@@ -1280,14 +1280,9 @@ void attn_dropout_mask_kernel(uint8_t* keep, DropArgs drop, int S, int64_t n_wor
 // Bound by reading K/V once, so the 32 MFMA columns of S^T[key][col] = K Q^T are (query position,
 // head within the KV group) pairs, col = i * G + g: all G query heads of a KV head ride on one read of
 // its K/V. A workgroup is ONE wave: column block x split x (b, kv head). It sweeps the split's
-// contiguous range of 64-key tiles through the forward's 2-slot LDS ring (2 workgroups = 128 KiB of
-// landing buffers per CU; the tile after the one being computed is in flight) and keeps the forward's
-// lane maps, swizzle and deferred running max. K/V rows at or past the column block's last visible key
-// + 1 are outside the buffer descriptors: never read, zeros in LDS. With a key mask, the V rows of
-// masked keys are zeroed in LDS, so nothing from a row no column sees reaches the P V product.
-// num_splits > 1: fp32 partials per (b*Hkv, column block, split), O [32 col][128 d] then {max, sum}
-// [32 col][2]; attn_decode_combine_kernel merges them in split order (no atomics). A split without a
-// visible key writes max = -inf, sum = 0 and no O; the combine selects such splits out.
+// contiguous range of 64-key tiles with the decode step below. K/V rows at or past the column block's
+// last visible key + 1 are outside the buffer descriptors: never read, zeros in LDS. Hidden keys are
+// those past the column's own position (key > qpos) and those the key mask clears.
 // ------------------------------------------------------------------------------------------------
 constexpr int kDecCols = 32;
 constexpr int kDecPartial = kDecCols * (kD + 2);           // floats per (b*Hkv, column block, split)
@@ -1315,9 +1310,126 @@ __device__ __forceinline__ float* dec_ws_ml(const DecArgs& a, int64_t nslots, in
     return a.ws + nslots * kDecCols * kD + (slot * kDecCols + col) * 2;
 }
 
+// The decode step, written once for attn_decode_kernel and attn_beams_kernel. The kernels differ in where
+// a tile's K / V come from, in the tile list and in which keys a column sees; the rest is here. Tiles go
+// through the forward's 2-slot LDS ring (2 workgroups = 128 KiB of landing buffers per CU; the tile after
+// the one being computed is in flight) with the forward's lane maps, swizzle and deferred running max: a
+// lane holds column l32 and the key rows (i & 3) + 8 ((i & 15) >> 2) + 32 (i >> 4) + 4 hi of a tile. Per
+// tile: dec_zero_unseen_v, dec_scores, the kernel's own selection of hidden keys (x = -inf), dec_softmax_pv.
+// num_splits > 1: fp32 partials per (b*Hkv, column block, split), O [32 col][128 d] then {max, sum}
+// [32 col][2]; attn_decode_combine_kernel merges them in split order (no atomics). A split without a
+// visible key writes max = -inf, sum = 0 and no O (dec_empty_split, dec_finish); the combine selects
+// such splits out.
+
+// the eight Q fragments of a column (qp: its row), zero for an unused column
+__device__ __forceinline__ void dec_load_q(bf16x8_t (&qf)[8], bool cvalid, const uint16_t* qp, int hi) {
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) qf[ks] = frag_or_zero(cvalid, qp + 16 * ks + 8 * hi);
+}
+
+// w_any: the tile's rows whose V stays. lane = the tile's row; the others are zeroed in LDS, so nothing
+// from a row no column sees reaches the P V product.
+__device__ __forceinline__ void dec_zero_unseen_v(uint8_t* V, uint64_t w_any, int lane) {
+    if (~w_any == 0ull) return;
+    if (!key_bit(w_any, lane)) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) *reinterpret_cast<u32x4_t*>(V + lane * kRowB + 16 * c) = u32x4_t{0u, 0u, 0u, 0u};
+    }
+    __syncthreads();
+}
+
+// S^T[key][col] = K Q^T of one tile, in the lane's 32 scores
+template <int F>
+__device__ __forceinline__ void dec_scores(float (&x)[32], const uint8_t* K, const bf16x8_t (&qf)[8], int l32, int hi) {
+    f32x16_t sc[2];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            sc[j] = mfma<F>(row_frag(K, 32 * j + l32, 32 * ks + 16 * hi), qf[ks], ks ? sc[j] : f32x16_t{});
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) x[16 * j + i] = sc[j][i];
+}
+
+// The online softmax over x (hidden keys at -inf) and O += P V. The running max moves only when the
+// tile's exceeds it by more than kFwdThr, and o is rescaled only in a tile where some lane's moved.
+template <int F>
+__device__ __forceinline__ void dec_softmax_pv(float (&x)[32], const uint8_t* V, TrLane tl, float sl2, float& m_run,
+                                               float& l_run, f32x16_t (&o)[4]) {
+    float mx = x[0];
+#pragma unroll
+    for (int i = 1; i < 32; ++i) mx = fmaxf(mx, x[i]);
+    const float m_tile = other_half_max(mx) * sl2;
+    const bool move = m_tile > m_run + kFwdThr;
+    const float m_new = move ? m_tile : m_run;
+    const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.f;
+    const float m_use = (m_new == kNegInf) ? 0.f : m_new;
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[i], sl2, -m_use));
+        sum += x[i];
+    }
+    l_run = l_run * alpha + sum;
+    m_run = m_new;
+    if (__builtin_amdgcn_ballot_w64(move) != 0) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
+    }
+    bf16x8_t pf[4];
+    pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[0]), pf[0], pf[1]);
+    pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[16]), pf[2], pf[3]);
+#pragma unroll
+    for (int n = 0; n < 16; ++n) o[n >> 2] = mfma<F>(tr_frag(V, tl, 16 * (n & 3), 32 * (n >> 2)), pf[n & 3], o[n >> 2]);
+}
+
+// A split without a tile (never with DIRECT); slot of nslots: the workgroup's partial, in the [b * Hkv]
+// [column block][split] order. The test on DIRECT, cvalid and hi stays with the caller: inside this
+// function it changed how the beams kernel stores {max, sum} (scripts/diag/isa_compare.py).
+__device__ __forceinline__ void dec_empty_split(const DecArgs& a, int64_t nslots, int64_t slot, int l32) {
+    float* ml = dec_ws_ml(a, nslots, slot, l32);
+    ml[0] = kNegInf;
+    ml[1] = 0.f;
+}
+
+// DIRECT (one split): the normalised row to a.o + o_idx and, with a.lse, its log-sum-exp to a.lse[lse_idx].
+// Otherwise the split's partial: O as it is, then {max, sum}; max = -inf and no O without a visible key.
+template <int F, bool DIRECT>
+__device__ __forceinline__ void dec_finish(const DecArgs& a, const f32x16_t (&o)[4], float m_run, float l_run,
+                                           int64_t nslots, int64_t slot, bool cvalid, int l32, int hi, int64_t o_idx,
+                                           int64_t lse_idx) {
+    const float l_tot = halves_sum(l_run);
+    if (!cvalid) return;
+    if (DIRECT) {
+        store_row<F>(a.o + o_idx, o, l_tot > 0.f ? 1.f / l_tot : 0.f, hi);
+        if (a.lse && hi == 0) a.lse[lse_idx] = l_tot > 0.f ? m_run + __log2f(l_tot) : __builtin_huge_valf();
+    } else {
+        const bool any = l_tot > 0.f;
+        if (any) {
+            float* po = dec_ws_o(a, slot, l32);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(po + 32 * dt + 8 * g + 4 * hi) =
+                        float4{o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
+        }
+        if (hi == 0) {
+            float* ml = dec_ws_ml(a, nslots, slot, l32);
+            ml[0] = any ? m_run : kNegInf;
+            ml[1] = any ? l_tot : 0.f;
+        }
+    }
+}
+
 // Args = DecPosArgs (smt_attn_fwd_cached_pos): the position of row b's first query is
-// a.pos[b * a.pos_stride], read here and saturated into [0, cap - Sq] (cap = the K / V buffers' row count; Sq <= cap is checked by
-// the host) before anything is derived from it, so no address depends on an out-of-contract value.
+// a.pos[b * a.pos_stride], read here and saturated into [0, cap - Sq] (cap = the K / V buffers' row
+// count; Sq <= cap is checked by the host) before anything is derived from it, so no address depends on
+// an out-of-contract value.
 // The tile partition is then the one the host computes for that q_offset, and the grid is sized from
 // the capacity. With Args = DecArgs, a.q_offset and a.tps are taken as they are.
 template <bool KMASK, int F, bool DIRECT, class Args>
@@ -1347,24 +1459,15 @@ void attn_decode_kernel(Args a) {
     const int t0 = sp * tps, t1 = min((kv_end + kKV - 1) / kKV, t0 + tps);
     const int64_t nslots = (int64_t)gridDim.z * a.ncb * a.nsplit;
     const int64_t slot = ((int64_t)bh * a.ncb + cb) * a.nsplit + sp;
-    if (t0 >= t1) {                                            // an empty split (never with DIRECT)
-        if (!DIRECT && cvalid && hi == 0) {
-            float* ml = dec_ws_ml(a, nslots, slot, l32);
-            ml[0] = kNegInf;
-            ml[1] = 0.f;
-        }
+    if (t0 >= t1) {
+        if (!DIRECT && cvalid && hi == 0) dec_empty_split(a, nslots, slot, l32);
         return;
     }
-    const uint16_t* qp = a.q.p + b * a.q.sb + h * a.q.sh + (int64_t)qi * a.q.ss;
     const uint16_t* kp = a.k.p + b * a.k.sb + hk * a.k.sh;
     const uint16_t* vp = a.v.p + b * a.v.sb + hk * a.v.sh;
     const uint64_t* km = KMASK ? a.kmask + (int64_t)b * a.kmask_ld : nullptr;
     bf16x8_t qf[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-        if (cvalid) qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + 16 * ks + 8 * hi);
-        else qf[ks] = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
-    }
+    dec_load_q(qf, cvalid, a.q.p + b * a.q.sb + h * a.q.sh + (int64_t)qi * a.q.ss, hi);
     // the descriptors end with row kv_end - 1: later rows are never read (they land as zeros)
     const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(kp, (int64_t)(kv_end - 1) * a.k.ss * 2 + kRowB);
     const __amdgpu_buffer_rsrc_t rv = uniform_rsrc(vp, (int64_t)(kv_end - 1) * a.v.ss * 2 + kRowB);
@@ -1394,25 +1497,10 @@ void attn_decode_kernel(Args a) {
         uint64_t w = ~0ull;
         if (KMASK) {
             w = km[t];                                         // workgroup-uniform
-            if (~w != 0ull) {
-                if (!key_bit(w, lane)) {                       // lane = the tile's row: a masked key's V row
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) *reinterpret_cast<u32x4_t*>(V + lane * kRowB + 16 * c) = u32x4_t{0u, 0u, 0u, 0u};
-                }
-                __syncthreads();
-            }
+            dec_zero_unseen_v(V, w, lane);                     // the V rows of masked keys
         }
-        f32x16_t sc[2];
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                sc[j] = mfma<F>(row_frag(K, 32 * j + l32, 32 * ks + 16 * hi), qf[ks], ks ? sc[j] : f32x16_t{});
         float x[32];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) x[16 * j + i] = sc[j][i];
+        dec_scores<F>(x, K, qf, l32, hi);
         // hidden keys leave by selection: the causal edge (which covers the ragged end, qpos < kv_end)
         // and the key mask
 #pragma unroll
@@ -1420,69 +1508,12 @@ void attn_decode_kernel(Args a) {
             const int key = k0 + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * hi;
             if (key > qpos || (KMASK && !key_bit(w, key))) x[i] = kNegInf;
         }
-        float mx = x[0];
-#pragma unroll
-        for (int i = 1; i < 32; ++i) mx = fmaxf(mx, x[i]);
-        const float m_tile = other_half_max(mx) * a.sl2;
-        const bool move = m_tile > m_run + kFwdThr;
-        const float m_new = move ? m_tile : m_run;
-        const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.f;
-        const float m_use = (m_new == kNegInf) ? 0.f : m_new;
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[i], a.sl2, -m_use));
-            sum += x[i];
-        }
-        l_run = l_run * alpha + sum;
-        m_run = m_new;
-        if (__builtin_amdgcn_ballot_w64(move) != 0) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
-        }
-        bf16x8_t pf[4];
-        pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[0]), pf[0], pf[1]);
-        pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[16]), pf[2], pf[3]);
-#pragma unroll
-        for (int n = 0; n < 16; ++n) o[n >> 2] = mfma<F>(tr_frag(V, tl, 16 * (n & 3), 32 * (n >> 2)), pf[n & 3], o[n >> 2]);
+        dec_softmax_pv<F>(x, V, tl, a.sl2, m_run, l_run, o);
         vm_wait_all();
         __syncthreads();
     }
-    const float l_tot = halves_sum(l_run);
-    if (!cvalid) return;
-    if (DIRECT) {
-        const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
-        uint16_t* op = a.o + b * a.o_sb + h * a.o_sh + (int64_t)qi * a.o_ss;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                uint2 wd;
-                wd.x = pk16<F>(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv);
-                wd.y = pk16<F>(o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-                *reinterpret_cast<uint2*>(op + 32 * dt + 8 * g + 4 * hi) = wd;
-            }
-        if (a.lse && hi == 0)
-            a.lse[((int64_t)b * a.Hq + h) * a.Sq + qi] = l_tot > 0.f ? m_run + __log2f(l_tot) : __builtin_huge_valf();
-    } else {
-        const bool any = l_tot > 0.f;
-        if (any) {
-            float* po = dec_ws_o(a, slot, l32);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<float4*>(po + 32 * dt + 8 * g + 4 * hi) =
-                        float4{o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
-        }
-        if (hi == 0) {
-            float* ml = dec_ws_ml(a, nslots, slot, l32);
-            ml[0] = any ? m_run : kNegInf;
-            ml[1] = any ? l_tot : 0.f;
-        }
-    }
+    dec_finish<F, DIRECT>(a, o, m_run, l_run, nslots, slot, cvalid, l32, hi, b * a.o_sb + h * a.o_sh + (int64_t)qi * a.o_ss,
+                          ((int64_t)b * a.Hq + h) * a.Sq + qi);
 }
 
 // One workgroup per (column, b*Hkv), one thread per d: the splits' partials in split order.
@@ -1519,9 +1550,9 @@ void attn_decode_combine_kernel(DecArgs a) {
 // that is never reordered. The prompt's K / V is stored once per sample; the generated K / V of step
 // j sits in row j of the physical slot that wrote it, and anc[row][j] names the slot that holds the
 // step-j key of that row's hypothesis. The 32 columns of a workgroup are (beam, head within the KV
-// group) pairs of ONE (sample, KV head), col = beam * G + g, so the beam plays the part the query
-// position plays in attn_decode_kernel and the ring, the lane maps, the partials and the combine are
-// that kernel's. The tile list of a workgroup's (sample, KV head) is the prompt's 64-key tiles, then
+// group) pairs of ONE (sample, KV head), col = beam * G + g: the beam plays the part the query position
+// plays in attn_decode_kernel, and the tiles go through the same decode step (above), partials and
+// combine. The tile list of a workgroup's (sample, KV head) is the prompt's 64-key tiles, then
 // every slot's generated tiles, slot by slot: each physical row is fetched once per sample, whatever
 // the number of beams that see it, and nothing is gathered. Splits are contiguous ranges of that list.
 // Visibility is one 64-bit word per (column, tile): the prompt mask word for a prompt tile; for a
@@ -1568,8 +1599,8 @@ constexpr int kBeamPre = 8;                // beams of a column block whose ance
 // address depends on an out-of-contract value. gt, the tile list and the tiles per split are then the
 // ones the host computes for that T, and the grid is sized from the capacity. The body reads the three
 // through gen_T() / gen_gt() / gen_tps(): the kernel's own values here, a.T, a.gt and a.tps as they are
-// with Args = BeamArgs. Selections on the constant POS and not locals or lambdas: with these the BeamArgs
-// instances compile to the instructions they had before this form existed (scripts/diag/isa_compare.py).
+// with Args = BeamArgs. Selections on the constant POS and not locals or lambdas: those changed the code
+// of the BeamArgs instances, which read nothing from the device (scripts/diag/isa_compare.py).
 template <bool KMASK, int F, bool DIRECT, class Args>
 __global__ __launch_bounds__(64)
 void attn_beams_kernel(Args a) {
@@ -1598,25 +1629,14 @@ void attn_beams_kernel(Args a) {
     const int t0 = sp * gen_tps(), t1 = min(a.pt + a.nb * gen_gt(), t0 + gen_tps());
     const int64_t nslots = (int64_t)gridDim.z * a.ncb * a.nsplit;
     const int64_t slot = ((int64_t)bh * a.ncb + cb) * a.nsplit + sp;
-    if (t0 >= t1) {                                            // an empty split (never with DIRECT)
-        if (!DIRECT && cvalid && hi == 0) {
-            float* ml = dec_ws_ml(a, nslots, slot, l32);
-            ml[0] = kNegInf;
-            ml[1] = 0.f;
-        }
+    if (t0 >= t1) {
+        if (!DIRECT && cvalid && hi == 0) dec_empty_split(a, nslots, slot, l32);
         return;
     }
     const int64_t row0 = (int64_t)n * a.nb;                    // the sample's first row / slot
     const uint64_t* km = KMASK ? a.kmask + (int64_t)n * a.kmask_ld : nullptr;
     bf16x8_t qf[8];
-    {
-        const uint16_t* qp = a.q.p + n * a.q.sb + h * a.q.sh + (int64_t)(cvalid ? beam : 0) * a.q.ss;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            if (cvalid) qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + 16 * ks + 8 * hi);
-            else qf[ks] = __builtin_bit_cast(bf16x8_t, u32x4_t{0u, 0u, 0u, 0u});
-        }
-    }
+    dec_load_q(qf, cvalid, a.q.p + n * a.q.sb + h * a.q.sh + (int64_t)(cvalid ? beam : 0) * a.q.ss, hi);
     const uint32_t lds0 = lds_addr(lds);
     const TrLane tl = tr_lane(lane);
     f32x16_t o[4];
@@ -1688,24 +1708,9 @@ void attn_beams_kernel(Args a) {
         }
         uint8_t* K = lds + (t & 1) * 2 * kTileB;
         uint8_t* V = K + kTileB;
-        if (~w_any != 0ull) {
-            if (!key_bit(w_any, lane)) {                       // lane = the tile's row: a row no column sees
-#pragma unroll
-                for (int c = 0; c < 16; ++c) *reinterpret_cast<u32x4_t*>(V + lane * kRowB + 16 * c) = u32x4_t{0u, 0u, 0u, 0u};
-            }
-            __syncthreads();
-        }
-        f32x16_t sc[2];
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                sc[j] = mfma<F>(row_frag(K, 32 * j + l32, 32 * ks + 16 * hi), qf[ks], ks ? sc[j] : f32x16_t{});
+        dec_zero_unseen_v(V, w_any, lane);
         float x[32];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) x[16 * j + i] = sc[j][i];
+        dec_scores<F>(x, K, qf, l32, hi);
         // hidden keys leave by selection
         const uint64_t w_hi = w_col >> (4 * hi);
 #pragma unroll
@@ -1713,73 +1718,18 @@ void attn_beams_kernel(Args a) {
             const int key = 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2);       // + 4 * hi, shifted in above
             if (!key_bit(w_hi, key)) x[i] = kNegInf;
         }
-        float mx = x[0];
-#pragma unroll
-        for (int i = 1; i < 32; ++i) mx = fmaxf(mx, x[i]);
-        const float m_tile = other_half_max(mx) * a.sl2;
-        const bool move = m_tile > m_run + kFwdThr;
-        const float m_new = move ? m_tile : m_run;
-        const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.f;
-        const float m_use = (m_new == kNegInf) ? 0.f : m_new;
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[i], a.sl2, -m_use));
-            sum += x[i];
-        }
-        l_run = l_run * alpha + sum;
-        m_run = m_new;
-        if (__builtin_amdgcn_ballot_w64(move) != 0) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
-        }
-        bf16x8_t pf[4];
-        pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[0]), pf[0], pf[1]);
-        pack_b_frags<F>(*reinterpret_cast<const float(*)[16]>(&x[16]), pf[2], pf[3]);
-#pragma unroll
-        for (int nn = 0; nn < 16; ++nn)
-            o[nn >> 2] = mfma<F>(tr_frag(V, tl, 16 * (nn & 3), 32 * (nn >> 2)), pf[nn & 3], o[nn >> 2]);
+        dec_softmax_pv<F>(x, V, tl, a.sl2, m_run, l_run, o);
         vm_wait_all();
         vm_wait_all_known();                                   // pre of the next tile has landed (compiler-visible)
         __syncthreads();
         cur = nxt;
     }
-    const float l_tot = halves_sum(l_run);
-    if (!cvalid) return;
-    if (DIRECT) {
-        const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
-        uint16_t* op = a.o + n * a.o_sb + h * a.o_sh + (int64_t)beam * a.o_ss;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                uint2 wd;
-                wd.x = pk16<F>(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv);
-                wd.y = pk16<F>(o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-                *reinterpret_cast<uint2*>(op + 32 * dt + 8 * g + 4 * hi) = wd;
-            }
-        if (a.lse && hi == 0)
-            a.lse[(row0 + beam) * a.Hq + h] = l_tot > 0.f ? m_run + __log2f(l_tot) : __builtin_huge_valf();
-    } else {
-        const bool any = l_tot > 0.f;
-        if (any) {
-            float* po = dec_ws_o(a, slot, l32);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<float4*>(po + 32 * dt + 8 * g + 4 * hi) =
-                        float4{o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
-        }
-        if (hi == 0) {
-            float* ml = dec_ws_ml(a, nslots, slot, l32);
-            ml[0] = any ? m_run : kNegInf;
-            ml[1] = any ? l_tot : 0.f;
-        }
-    }
+    dec_finish<F, DIRECT>(a, o, m_run, l_run, nslots, slot, cvalid, l32, hi, n * a.o_sb + h * a.o_sh + (int64_t)beam * a.o_ss,
+                          (row0 + beam) * a.Hq + h);
 }
+#undef gen_T
+#undef gen_gt
+#undef gen_tps
 
 // smt_attn_kv_append_pos: one step's K and V, [R][Hkv][1][128] each, into row clamp(*steps, 1, cap) - 1 of
 // the generated buffers [R][Hkv][cap][128]. One thread per 16-byte piece of a (tensor, row, head); the
@@ -1803,10 +1753,6 @@ void attn_kv_append_kernel(AppendArgs a) {
     const u32x4_t w = *reinterpret_cast<const u32x4_t*>(src.p + r * src.sb + h * src.sh + 8 * piece);
     *reinterpret_cast<u32x4_t*>(const_cast<uint16_t*>(dst.p) + r * dst.sb + h * dst.sh + (int64_t)(s - 1) * dst.ss + 8 * piece) = w;
 }
-
-#undef gen_T
-#undef gen_gt
-#undef gen_tps
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -1992,17 +1938,67 @@ int dec_col_blocks(const smt_attn_shape* s, int32_t Sq) {
 // the grid has that many, but never below kDecMinTiles tiles per split (a split's fixed cost: the Q
 // load, a first tile nothing overlaps, its partials and their combine).
 constexpr int kDecWgSlots = 512, kDecMinTiles = 2;
-int dec_default_splits(const smt_attn_shape* s, int32_t Sq) {
-    const int64_t base = (int64_t)s->B * s->Hkv * dec_col_blocks(s, Sq);
-    const int64_t tiles = ((int64_t)s->S + kKV - 1) / kKV;
-    int64_t n = (kDecWgSlots + base - 1) / base;
+int default_splits(int64_t base_workgroups, int64_t tiles) {
+    int64_t n = (kDecWgSlots + base_workgroups - 1) / base_workgroups;
     if (n > tiles / kDecMinTiles) n = tiles / kDecMinTiles;
     return n < 1 ? 1 : (int)n;
+}
+int dec_default_splits(const smt_attn_shape* s, int32_t Sq) {
+    return default_splits((int64_t)s->B * s->Hkv * dec_col_blocks(s, Sq), ((int64_t)s->S + kKV - 1) / kKV);
 }
 
 int64_t dec_workspace(const smt_attn_shape* s, int32_t Sq, int32_t num_splits) {
     if (num_splits <= 1) return 0;
     return (int64_t)s->B * s->Hkv * dec_col_blocks(s, Sq) * num_splits * kDecPartial * (int64_t)sizeof(float);
+}
+
+// The split count of a call (num_splits, or fallback for 0) and the workspace it needs; ws_fn names the
+// entry point that sizes the workspace.
+int check_splits(const char* fn, int32_t num_splits, int fallback, const void* workspace, const char* ws_fn, int* nsplit) {
+    if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
+    const int n = *nsplit = num_splits ? num_splits : fallback;
+    if (n > 65535) return fail(-1, "%s: num_splits = %d is above 65535", fn, n);
+    if (n > 1 && !workspace) return fail(-1, "%s: null workspace with %d splits (%s bytes)", fn, n, ws_fn);
+    if (n > 1 && !al16(workspace)) return fail(-2, "%s: workspace needs 16-byte alignment", fn);
+    return 0;
+}
+
+// the fields of DecArgs that both decode launchers fill alike; Sq: the query positions, or the beams
+void fill_dec_common(DecArgs& a, const smt_attn_tensor* o, int64_t o_sb, int64_t o_ss, float* lse, void* workspace,
+                     const smt_attn_shape* shape, int32_t Sq, int nsplit) {
+    a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o_sb; a.o_sh = o->sh; a.o_ss = o_ss;
+    a.lse = lse;
+    a.ws = static_cast<float*>(workspace);
+    a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.G = shape->Hq / shape->Hkv;
+    a.Sq = Sq; a.ncols = Sq * a.G; a.ncb = dec_col_blocks(shape, Sq); a.nsplit = nsplit;
+    a.sl2 = shape->scale * 1.4426950408889634f;
+}
+
+// The kernel of an argument struct, and the launch both decode launchers end with: a (by_pos: ap, the
+// device-position form of the same call) on the grid column block x split x (b, kv head), then the combine
+// of the splits' partials. The beams' combine writes lse by rows (ROWS).
+template <bool KMASK, int F, bool DIRECT, class Args>
+constexpr auto decode_kernel() {
+    if constexpr (std::is_base_of<BeamArgs, Args>::value) return attn_beams_kernel<KMASK, F, DIRECT, Args>;
+    else return attn_decode_kernel<KMASK, F, DIRECT, Args>;
+}
+template <class Args, class PosArgs>
+int launch_decode(const Args& a, const PosArgs& ap, bool by_pos, const smt_attn_shape* shape, hipStream_t stream) {
+    constexpr bool ROWS = std::is_base_of<BeamArgs, Args>::value;
+    const unsigned bh = (unsigned)(shape->B * shape->Hkv);
+    const dim3 grid((unsigned)a.ncb, (unsigned)a.nsplit, bh);
+    dispatch(shape->dtype, [&](auto f, auto km, auto direct, auto pos_form) {
+        if constexpr (pos_form())
+            hipLaunchKernelGGL((decode_kernel<km(), f(), direct(), PosArgs>()), grid, dim3(64), 0, stream, ap);
+        else hipLaunchKernelGGL((decode_kernel<km(), f(), direct(), Args>()), grid, dim3(64), 0, stream, a);
+    }, a.kmask != nullptr, a.nsplit == 1, by_pos);
+    int rc;
+    if ((rc = check_launch(ROWS ? "attn_beams_kernel" : "attn_decode_kernel")) || a.nsplit == 1) return rc;
+    dispatch(shape->dtype, [&](auto f) {
+        hipLaunchKernelGGL((attn_decode_combine_kernel<f(), ROWS>), dim3((unsigned)a.ncols, bh), dim3(kD), 0, stream,
+                           static_cast<const DecArgs&>(a));
+    });
+    return check_launch("attn_decode_combine_kernel");
 }
 
 // smt_attn_fwd_cached (pos == nullptr: the position is q_offset) and smt_attn_fwd_cached_pos (the
@@ -2029,13 +2025,10 @@ int attn_fwd_cached(const char* fn, const smt_attn_tensor* q, const smt_attn_ten
             return fail(-1, "%s: q_offset %d + Sq %d > Skv %d (a query without a key slot of its own)", fn, (int)q_offset,
                         (int)Sq, Skv);
     }
-    if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
-    if ((rc = check_kmask_ld(fn, key_mask, key_mask_ld, Skv, "Skv"))) return rc;
-    const int nsplit = num_splits ? num_splits : dec_default_splits(shape, Sq);
-    if (nsplit > 65535) return fail(-1, "%s: num_splits = %d is above 65535", fn, nsplit);
-    if (nsplit > 1 && !workspace)
-        return fail(-1, "%s: null workspace with %d splits (smt_attn_cached_workspace bytes)", fn, nsplit);
-    if (nsplit > 1 && !al16(workspace)) return fail(-2, "%s: workspace needs 16-byte alignment", fn);
+    int nsplit;
+    if ((rc = check_kmask_ld(fn, key_mask, key_mask_ld, Skv, "Skv")) ||
+        (rc = check_splits(fn, num_splits, dec_default_splits(shape, Sq), workspace, "smt_attn_cached_workspace", &nsplit)))
+        return rc;
     // keys any query of the call sees: [0, kv_all); a device position can reach the whole capacity
     const int kv_all = by_pos ? Skv : q_offset + Sq;
     if ((int64_t)kv_all * k->ss * 2 >= 0x7fffffffLL || (int64_t)kv_all * v->ss * 2 >= 0x7fffffffLL)
@@ -2044,32 +2037,16 @@ int attn_fwd_cached(const char* fn, const smt_attn_tensor* q, const smt_attn_ten
     const int64_t bh = (int64_t)shape->B * shape->Hkv;
     if (ncols > 0x7fffffffLL / 2 || bh > 65535) return fail(-1, "%s: B * Hkv must stay within 65535 and Sq * G below 2^30", fn);
     DecArgs a;
+    fill_dec_common(a, o, o->sb, o->ss, lse, workspace, shape, Sq, nsplit);
     a.q = tns(q); a.k = tns(k); a.v = tns(v);
-    a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o->sb; a.o_sh = o->sh; a.o_ss = o->ss;
-    a.lse = lse;
     a.kmask = key_mask; a.kmask_ld = key_mask_ld;
-    a.ws = static_cast<float*>(workspace);
-    a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.G = shape->Hq / shape->Hkv;
-    a.Sq = Sq; a.q_offset = by_pos ? 0 : q_offset;
-    a.ncols = (int)ncols; a.ncb = dec_col_blocks(shape, Sq); a.nsplit = nsplit;
+    a.q_offset = by_pos ? 0 : q_offset;
     const int tiles = (kv_all + kKV - 1) / kKV;
     a.tps = (tiles + nsplit - 1) / nsplit;                 // by_pos: the kernel's own, from its position
-    a.sl2 = shape->scale * 1.4426950408889634f;
-    const dim3 grid((unsigned)a.ncb, (unsigned)nsplit, (unsigned)bh);
     DecPosArgs ap;                                         // the device-position form of the same call
     static_cast<DecArgs&>(ap) = a;
     ap.pos = pos; ap.pos_stride = pos_stride; ap.cap = Skv;
-    dispatch(shape->dtype, [&](auto f, auto km, auto direct, auto pos_form) {
-        if constexpr (pos_form())
-            hipLaunchKernelGGL((attn_decode_kernel<km(), f(), direct(), DecPosArgs>), grid, dim3(64), 0, stream, ap);
-        else hipLaunchKernelGGL((attn_decode_kernel<km(), f(), direct(), DecArgs>), grid, dim3(64), 0, stream, a);
-    }, key_mask != nullptr, nsplit == 1, by_pos);
-    if ((rc = check_launch("attn_decode_kernel")) || nsplit == 1) return rc;
-    const dim3 cgrid((unsigned)ncols, (unsigned)bh);
-    dispatch(shape->dtype, [&](auto f) {
-        hipLaunchKernelGGL(attn_decode_combine_kernel<f()>, cgrid, dim3(kD), 0, stream, a);
-    });
-    return check_launch("attn_decode_combine_kernel");
+    return launch_decode(a, ap, by_pos, shape, stream);
 }
 
 // Beam-shared cache: the shape (S is not used), the beam count and the fill levels. Host arithmetic only.
@@ -2094,11 +2071,7 @@ int beam_col_blocks(const smt_attn_shape* s, int32_t nb) { return dec_col_blocks
 int beam_tiles(int32_t nb, int32_t P, int32_t T) { return (P + kKV - 1) / kKV + nb * ((T + kKV - 1) / kKV); }
 // as dec_default_splits, over the tile list of one (sample, KV head)
 int beam_default_splits(const smt_attn_shape* s, int32_t nb, int32_t P, int32_t T) {
-    const int64_t base = (int64_t)s->B * s->Hkv * beam_col_blocks(s, nb);
-    const int64_t tiles = beam_tiles(nb, P, T);
-    int64_t n = (kDecWgSlots + base - 1) / base;
-    if (n > tiles / kDecMinTiles) n = tiles / kDecMinTiles;
-    return n < 1 ? 1 : (int)n;
+    return default_splits((int64_t)s->B * s->Hkv * beam_col_blocks(s, nb), beam_tiles(nb, P, T));
 }
 
 // smt_attn_fwd_beams (by_pos false: T is the host's) and smt_attn_fwd_beams_pos (the kernel reads *steps;
@@ -2121,52 +2094,31 @@ int attn_fwd_beams(const char* fn, const smt_attn_tensor* q, const smt_attn_tens
     if (by_pos && !steps) return fail(-1, "%s: null steps", fn);
     if (by_pos && (reinterpret_cast<uintptr_t>(steps) & 3u)) return fail(-2, "%s: steps needs 4-byte alignment (int32)", fn);
     if (anc_ld < T) return fail(-1, "%s: anc_ld %lld < %s %d", fn, (long long)anc_ld, by_pos ? "T_cap" : "T", (int)T);
-    if (num_splits < 0) return fail(-1, "%s: num_splits = %d is negative", fn, (int)num_splits);
-    if ((rc = check_kmask_ld(fn, prompt_mask, prompt_mask_ld, P, "P"))) return rc;
-    const int nsplit = num_splits ? num_splits : beam_default_splits(shape, nb, P, T);
-    if (nsplit > 65535) return fail(-1, "%s: num_splits = %d is above 65535", fn, nsplit);
-    if (nsplit > 1 && !workspace)
-        return fail(-1, "%s: null workspace with %d splits (smt_attn_beams_workspace bytes)", fn, nsplit);
-    if (nsplit > 1 && !al16(workspace)) return fail(-2, "%s: workspace needs 16-byte alignment", fn);
+    int nsplit;
+    if ((rc = check_kmask_ld(fn, prompt_mask, prompt_mask_ld, P, "P")) ||
+        (rc = check_splits(fn, num_splits, beam_default_splits(shape, nb, P, T), workspace, "smt_attn_beams_workspace", &nsplit)))
+        return rc;
     // a tile's 64 rows are addressed with 32-bit byte offsets from the head's first row
     const auto span = [](int rows, int64_t ss) { return ((int64_t)rows + kKV) * ss * 2 >= 0x7fffffffLL; };
     if (P > 0 && (span(P, kp->ss) || span(P, vp->ss)))
         return fail(-2, "%s: the P rows of k_prompt / v_prompt of one head must span less than 2 GiB", fn);
     if (span(T, kg->ss) || span(T, vg->ss))
         return fail(-2, "%s: the T rows of k_gen / v_gen of one head must span less than 2 GiB", fn);
-    const int G = shape->Hq / shape->Hkv;
-    const int64_t bh = (int64_t)shape->B * shape->Hkv;
     BeamArgs a;
+    fill_dec_common(a, o, o->sb * nb, o->sb, lse, workspace, shape, nb, nsplit);
     a.q = tns(q); a.q.ss = q->sb; a.q.sb = q->sb * nb;         // the beam as the "query position" of sample n
     a.k = P > 0 ? tns(kp) : Tns{nullptr, 0, 0, 0}; a.v = P > 0 ? tns(vp) : Tns{nullptr, 0, 0, 0};
     a.kg = tns(kg); a.vg = tns(vg);
-    a.o = static_cast<uint16_t*>(o->ptr); a.o_sb = o->sb * nb; a.o_sh = o->sh; a.o_ss = o->sb;
-    a.lse = lse;
     a.kmask = P > 0 ? prompt_mask : nullptr; a.kmask_ld = prompt_mask_ld;
-    a.ws = static_cast<float*>(workspace);
-    a.Hq = shape->Hq; a.Hkv = shape->Hkv; a.G = G;
-    a.Sq = nb; a.q_offset = 0;
-    a.ncols = nb * G; a.ncb = beam_col_blocks(shape, nb); a.nsplit = nsplit;
+    a.q_offset = 0;
     a.anc = anc; a.anc_ld = anc_ld;
     a.nb = nb; a.P = P; a.T = T;
     a.pt = (P + kKV - 1) / kKV; a.gt = (T + kKV - 1) / kKV;
     a.tps = (beam_tiles(nb, P, T) + nsplit - 1) / nsplit;
-    a.sl2 = shape->scale * 1.4426950408889634f;
-    const dim3 grid((unsigned)a.ncb, (unsigned)nsplit, (unsigned)bh);
     BeamPosArgs ap;                                        // the device-counter form of the same call
     static_cast<BeamArgs&>(ap) = a;
     ap.steps = steps;
-    dispatch(shape->dtype, [&](auto f, auto km, auto direct, auto pos_form) {
-        if constexpr (pos_form())
-            hipLaunchKernelGGL((attn_beams_kernel<km(), f(), direct(), BeamPosArgs>), grid, dim3(64), 0, stream, ap);
-        else hipLaunchKernelGGL((attn_beams_kernel<km(), f(), direct(), BeamArgs>), grid, dim3(64), 0, stream, a);
-    }, a.kmask != nullptr, nsplit == 1, by_pos);
-    if ((rc = check_launch("attn_beams_kernel")) || nsplit == 1) return rc;
-    const dim3 cgrid((unsigned)a.ncols, (unsigned)bh);
-    dispatch(shape->dtype, [&](auto f) {
-        hipLaunchKernelGGL((attn_decode_combine_kernel<f(), true>), cgrid, dim3(kD), 0, stream, static_cast<const DecArgs&>(a));
-    });
-    return check_launch("attn_decode_combine_kernel");
+    return launch_decode(a, ap, by_pos, shape, stream);
 }
 
 }  // namespace
