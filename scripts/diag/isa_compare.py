@@ -15,8 +15,10 @@ symbol, its instruction lines with basic-block labels and comments stripped (lab
 between builds). ``diff`` pairs kernels by demangled name after applying ``--map`` substitutions
 (a template parameter added with its old value, e.g. ``--map "<4, false>=<4, false, 0>"``) and prints
 identical / differing / unmatched kernels; for a differing kernel also the per-mnemonic count deltas and
-its register, scratch and LDS figures (the assembly metadata's, kept by ``dump``) before and after. Exit
-status 1 when any paired kernel differs."""
+its register, scratch and LDS figures (the assembly metadata's, kept by ``dump``) before and after, and
+where it differs: the first and last differing instruction and how many of the diff blocks lie between
+the first and last ``v_mfma`` (the hot loop). Exit status 1 when any paired kernel differs."""
+import difflib
 import json
 import os
 import re
@@ -99,6 +101,15 @@ def diff(a, b, maps):
         ca, cb = (Counter(i.split()[0] for i in k[n]["ins"]) for k in (Am, B))
         print("    counts:", " ".join(f"{m} {cb[m] - ca[m]:+d}" for m in sorted(ca | cb) if ca[m] != cb[m]) or "equal")
         print("    meta:  ", " ".join(f"{k} {Am[n]['meta'].get(k)} -> {B[n]['meta'].get(k)}" for k in META))
+        # where it differs (indices into the listing before): did the hot loop move?
+        ia = Am[n]["ins"]
+        blocks = [op for op in difflib.SequenceMatcher(None, ia, B[n]["ins"], autojunk=False).get_opcodes()
+                  if op[0] != "equal"]
+        mf = [i for i, x in enumerate(ia) if x.startswith("v_mfma")]
+        hot = sum(1 for _, i1, i2, _, _ in blocks if mf and i1 <= mf[-1] and max(i2, i1 + 1) > mf[0])
+        print(f"    where:   first {blocks[0][1]}, last {max(blocks[-1][2] - 1, blocks[-1][1])} of {len(ia)}; "
+              f"{len(blocks)} diff blocks, {hot} between the first and last v_mfma"
+              + (f" ({mf[0]}..{mf[-1]})" if mf else ""))
     for n in missing:
         print("unmatched ", n)
     print(f"{len(same)} identical, {len(differ)} different, {len(missing)} unmatched of {len(Am)} before; "

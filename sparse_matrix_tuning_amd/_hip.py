@@ -378,20 +378,12 @@ def tile_wgrad(grad_out2d: torch.Tensor, x: torch.Tensor, tile_rc: torch.Tensor,
     if out.numel() != n * TILE_ELEMS:
         raise ValueError(f"tile_wgrad: out has {out.numel()} elements, expected {n * TILE_ELEMS}")
     T = grad_out2d.shape[0]
-    if x.dim() == 3:                      # block-major [n_cb, T, 256]
-        if not x.is_contiguous() or x.shape[1:] != (T, BLOCK):
-            raise ValueError("tile_wgrad: a block-major x must be a contiguous [n_cb, T, 256] tensor")
-        ld_x, xbs = BLOCK, T * BLOCK
-    else:
-        if x.dim() != 2 or x.shape[0] != T or x.stride(1) != 1:
-            raise ValueError("tile_wgrad: x must be [T, features] with unit feature stride")
-        ld_x, xbs = x.stride(0), BLOCK
+    ld_x, xbs = _wgrad_x_layout(x, T, "tile_wgrad")
     if grad_out2d.stride(1) != 1:
         raise ValueError("tile_wgrad: grad_out must be [T, features] with unit feature stride")
     ws_bytes = wgrad_workspace_bytes(T, n)
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
-        raise ValueError("tile_wgrad: order must be int32 [n_tiles]")
+    ws = _workspace(ws_bytes, dev)
+    _check_order("tile_wgrad", order, n)
     rc = load().smt_tile_wgrad(_ptr(grad_out2d), grad_out2d.stride(0), _ptr(x), ld_x, xbs, T,
                                _ptr(tile_rc), _ptr(order), n, _ptr(out), _DT[out.dtype], int(bool(accumulate)),
                                _ptr(ws), ws_bytes, _stream(dev))
@@ -408,6 +400,16 @@ def _wgrad_x_layout(x: torch.Tensor, T: int, what: str):
     if x.dim() != 2 or x.shape[0] != T or x.stride(1) != 1:
         raise ValueError(f"{what}: x must be [T, features] with unit feature stride")
     return x.stride(0), BLOCK
+
+
+def _check_order(fn: str, order: Optional[torch.Tensor], n: int) -> None:
+    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
+        raise ValueError(f"{fn}: order must be int32 [n_tiles]")
+
+
+def _workspace(nbytes: int, dev: torch.device) -> torch.Tensor:
+    """The launch's slab workspace (never empty: the ABI takes its pointer)."""
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
 
 
 def tile_wgrad_batch(items: Sequence[tuple], tile_tab: torch.Tensor, order: Optional[torch.Tensor] = None,
@@ -446,19 +448,18 @@ def tile_wgrad_batch(items: Sequence[tuple], tile_tab: torch.Tensor, order: Opti
     if tile_tab.dtype != torch.int32 or tile_tab.dim() != 2 or tile_tab.shape[1] != 4:
         raise ValueError("tile_wgrad_batch: tile_tab must be int32 [n, 4]")
     n = tile_tab.shape[0]
-    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
-        raise ValueError("tile_wgrad_batch: order must be int32 [n_tiles]")
+    _check_order("tile_wgrad_batch", order, n)
     if seq_len:
         if T % int(seq_len):
             raise ValueError(f"tile_wgrad_batch: T = {T} is not a whole number of {seq_len}-row samples")
         ws_bytes = int(load().smt_wgrad_seq_workspace_bytes(T, int(seq_len), n))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        ws = _workspace(ws_bytes, dev)
         rc = load().smt_tile_wgrad_batch_seq(mods, len(items), T, int(seq_len), _ptr(tile_tab), _ptr(order), n,
                                              _DT[out_dtype], _ptr(ws), ws_bytes, _stream(dev))
         _check(rc, "smt_tile_wgrad_batch_seq")
         return
     ws_bytes = int(load().smt_wgrad_batch_workspace_bytes(T, n))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(ws_bytes, dev)
     rc = load().smt_tile_wgrad_batch(mods, len(items), T, _ptr(tile_tab), _ptr(order), n, _DT[out_dtype],
                                      _ptr(ws), ws_bytes, _stream(dev))
     _check(rc, "smt_tile_wgrad_batch")
@@ -569,11 +570,10 @@ def tile_wgrad_mx(g: MxBlocks, x: MxBlocks, tile_rc: torch.Tensor, out: torch.Te
         raise ValueError(f"tile_wgrad_mx: out has {out.numel()} elements, expected {n * TILE_ELEMS}")
     if g.T != x.T or g.ldq != x.ldq:
         raise ValueError("tile_wgrad_mx: operands cover different rows")
-    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
-        raise ValueError("tile_wgrad_mx: order must be int32 [n_tiles]")
+    _check_order("tile_wgrad_mx", order, n)
     ldq = g.ldq
     ws_bytes = load().smt_wgrad_mx_workspace_bytes(ldq, n)
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(ws_bytes, dev)
     rc = load().smt_tile_wgrad_mx(_ptr(g.q), _ptr(g.scales), _ptr(x.q), _ptr(x.scales), ldq, _ptr(tile_rc),
                                   _ptr(order), n, _ptr(out), _DT[out.dtype], int(bool(accumulate)), _ptr(ws),
                                   ws_bytes, _stream(dev))
@@ -602,10 +602,9 @@ def tile_wgrad_mx_batch(items: Sequence[tuple], tile_tab: torch.Tensor, order: O
     if tile_tab.dtype != torch.int32 or tile_tab.dim() != 2 or tile_tab.shape[1] != 4:
         raise ValueError("tile_wgrad_mx_batch: tile_tab must be int32 [n, 4]")
     n = tile_tab.shape[0]
-    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
-        raise ValueError("tile_wgrad_mx_batch: order must be int32 [n_tiles]")
+    _check_order("tile_wgrad_mx_batch", order, n)
     ws_bytes = int(load().smt_wgrad_mx_workspace_bytes(ldq, n))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(ws_bytes, dev)
     rc = load().smt_tile_wgrad_mx_batch(mods, len(items), ldq, _ptr(tile_tab), _ptr(order), n, _DT[out_dtype],
                                         _ptr(ws), ws_bytes, _stream(dev))
     _check(rc, "smt_tile_wgrad_mx_batch")

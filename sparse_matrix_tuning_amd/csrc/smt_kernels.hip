@@ -111,8 +111,10 @@ constexpr int kImgBytes = kBK * kRowBytes;     // 32 KiB per operand per stage
 constexpr int kChunksPerThread = (kImgBytes / 16) / kWgThreads;   // 4 x 16 B per operand
 static_assert(kChunksPerThread == 4, "staging geometry");
 
+// ROW_BYTES: 512 (a whole 256-feature slice row) or 256 (the quarter kernels' half-slice row)
+template <int ROW_BYTES>
 __device__ __forceinline__ uint32_t img_off(uint32_t k, uint32_t byte_in_row) {
-    return k * kRowBytes + (byte_in_row ^ ((k & 3u) << 6));
+    return k * ROW_BYTES + (byte_in_row ^ ((k & 3u) << 6));
 }
 
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
@@ -127,13 +129,25 @@ __device__ __forceinline__ f32x16_t mfma16(const bf16x8_t& a, const bf16x8_t& b,
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+template <int ROW_BYTES>
 __device__ __forceinline__ bf16x8_t tr_frag(const uint8_t* img, uint32_t k, uint32_t byte_in_row) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(img + img_off(k, byte_in_row)));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(img + img_off(k + 4, byte_in_row)));
+    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(img + img_off<ROW_BYTES>(k, byte_in_row)));
+    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(img + img_off<ROW_BYTES>(k + 4, byte_in_row)));
     // whole-vector bit casts: element-wise __bf16 bit_casts of vector lanes miscompile (all lanes
     // came back equal to element 0 on ROCm 7.2 / gfx950)
     const s16x8_t both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8_t, both);
+}
+
+// tr-read lane geometry: group gi = lane>>4 covers feature offset 16*(gi&1) and k offset
+// 8*(gi>>1); lane 4q+p of the group supplies row q, features 4p..4p+3 (T10).
+struct TrLane { uint32_t feat_byte, krow; };
+
+__device__ __forceinline__ TrLane tr_lane(int lane) {
+    const int gi = lane >> 4;
+    const int q = (lane >> 2) & 3;
+    const int p = lane & 3;
+    return {2u * (16u * (gi & 1) + 4u * p), 8u * (gi >> 1) + q};
 }
 
 // Epilogue modes: partial slab (S > 1), or the final tile written directly (S == 1). kOutSlabBF16:
@@ -222,34 +236,79 @@ __device__ __forceinline__ void wgrad_store_t(f32x16_t (&acc)[MB][2], void* __re
 // of one module (BATCH = false: int32 [n][2] table of (row_block, col_block), module m[0]) or of up
 // to SMT_WGRAD_MAX_MODULES modules that share T (BATCH = true: int32 [n][4] table of (module,
 // row_block, col_block, tile index in that module's output)). Everything here is workgroup-uniform.
-struct WgradModules { smt_wgrad_module m[SMT_WGRAD_MAX_MODULES]; };
-struct WgradMxModules { smt_wgrad_mx_module m[SMT_WGRAD_MAX_MODULES]; };   // the MX-fp8 kernels
+// kSeqRounding: whether the launches of these modules know the reference rounding (wgrad_span; the
+// MX-fp8 kernels have none: their splits are plain chunks of T and their slabs always fp32).
+struct WgradModules { smt_wgrad_module m[SMT_WGRAD_MAX_MODULES]; static constexpr bool kSeqRounding = true; };
+struct WgradMxModules { smt_wgrad_mx_module m[SMT_WGRAD_MAX_MODULES]; static constexpr bool kSeqRounding = false; };
 
+struct WgradTabRow { int mi, r, c, ti; };   // module, row block, column block, tile index in the module's output
+
+template <bool BATCH>
+__device__ __forceinline__ WgradTabRow wgrad_tab_row(const int32_t* __restrict__ tab, int tile) {
+    if (BATCH) return {tab[4 * tile], tab[4 * tile + 1], tab[4 * tile + 2], tab[4 * tile + 3]};
+    return {0, tab[2 * tile], tab[2 * tile + 1], tile};
+}
+
+// tile ti of a module's output (either modules struct)
+template <int OUT_BYTES, typename M>
+__device__ __forceinline__ void* wgrad_out(const M& m, int ti) {
+    return static_cast<uint8_t*>(m.grad_tiles) + (int64_t)ti * kTileElems * OUT_BYTES;
+}
+
+// E: the operands' element type (uint16_t: raw bf16 / fp16 bits; float: wgrad_f32_kernel)
+template <typename E>
 struct WgradTile {
-    const uint16_t* g;       // grad_out column slice r: element (t, j) at g[t * ldg + j]
-    const uint16_t* x;       // input column block c: element (t, j) at x[t * ldx + j]
+    const E* g;              // grad_out column slice r: element (t, j) at g[t * ldg + j]
+    const E* x;              // input column block c: element (t, j) at x[t * ldx + j]
     int64_t ldg, ldx;
-    void* out;               // the final tile (S == 1 epilogue and the reduce)
+    void* out;               // the final tile (S == 1 epilogue)
     int accumulate;
 };
 
-template <bool BATCH, int OUT_BYTES>
-__device__ __forceinline__ WgradTile wgrad_tile(const WgradModules& mods, const int32_t* __restrict__ tab, int tile) {
-    WgradTile t;
-    int mi = 0, r, c, ti;
-    if (BATCH) {
-        mi = tab[4 * tile]; r = tab[4 * tile + 1]; c = tab[4 * tile + 2]; ti = tab[4 * tile + 3];
-    } else {
-        r = tab[2 * tile]; c = tab[2 * tile + 1]; ti = tile;
-    }
-    const smt_wgrad_module& m = mods.m[mi];
+template <bool BATCH, int OUT_BYTES, typename E = uint16_t>
+__device__ __forceinline__ WgradTile<E> wgrad_tile(const WgradModules& mods, const int32_t* __restrict__ tab, int tile) {
+    const WgradTabRow row = wgrad_tab_row<BATCH>(tab, tile);
+    const smt_wgrad_module& m = mods.m[row.mi];
+    WgradTile<E> t;
     t.ldg = m.ld_grad_out;
     t.ldx = m.ld_x;
-    t.g = static_cast<const uint16_t*>(m.grad_out) + (int64_t)r * kTile;
-    t.x = static_cast<const uint16_t*>(m.x) + (int64_t)c * m.x_block_stride;
-    t.out = static_cast<uint8_t*>(m.grad_tiles) + (int64_t)ti * kTileElems * OUT_BYTES;
+    t.g = static_cast<const E*>(m.grad_out) + (int64_t)row.r * kTile;
+    t.x = static_cast<const E*>(m.x) + (int64_t)row.c * m.x_block_stride;
+    t.out = wgrad_out<OUT_BYTES>(m, row.ti);
     t.accumulate = m.accumulate;
     return t;
+}
+
+// The work of one workgroup: XCD-aware, chunk-major schedule. Workgroups are dealt round-robin over
+// the 8 XCDs (b and b+8 share one); the bijective remap (cdna_hip_programming T1) gives each XCD a
+// CONTIGUOUS run of logical ids L = s*n_tiles + i: the tiles of (about) one T-chunk, in `order` (the
+// host sorts tiles so that those sharing an x column-block / g row-block are adjacent). Tiles running
+// on one XCD therefore stream the same rows at the same time and re-read shared slices from that
+// XCD's L2 instead of HBM. QUARTER (a workgroup owns a 128x128 quarter qd = 2*qm + qn of its tile):
+// L = (s*n_tiles + i)*4 + qd, so the four quarters of a (tile, chunk) run on one XCD together.
+// Placement only changes speed, never results.
+struct WgradWork { int tile, s, qd; };
+
+template <bool QUARTER>
+__device__ __forceinline__ WgradWork wgrad_work(int n_tiles, int S, const int32_t* __restrict__ order) {
+    const int total = n_tiles * S * (QUARTER ? 4 : 1);
+    const int b = blockIdx.x;
+    const int q8 = total >> 3, r8 = total & 7, xcd = b & 7;
+    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
+    const int ts = QUARTER ? L >> 2 : L;
+    const int s = ts / n_tiles;
+    const int li = ts - s * n_tiles;
+    return {order != nullptr ? order[li] : li, s, QUARTER ? L & 3 : 0};
+}
+
+template <int MB>
+__device__ __forceinline__ void wgrad_zero(f32x16_t (&acc)[MB][2]) {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 }
 
 // Rows [t_begin, t_end) of split s. Default (seq == 0): contiguous chunks of T. Reference rounding
@@ -276,20 +335,9 @@ void wgrad_partial_kernel(const WgradModules mods, int64_t T, int64_t chunk, int
                           float* __restrict__ slab) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 2 * kImgBytes];   // 128 KiB, one array
 
-    // XCD-aware, chunk-major schedule. Workgroups are dealt round-robin over the 8 XCDs (b and b+8
-    // share one); the bijective remap (cdna_hip_programming T1) gives each XCD a CONTIGUOUS run of
-    // logical ids L = s*n_tiles + i: the tiles of (about) one T-chunk, in `order` (the host sorts
-    // tiles so that those sharing an x column-block / g row-block are adjacent). Tiles running on
-    // one XCD therefore stream the same rows at the same time and re-read shared slices from that
-    // XCD's L2 instead of HBM. Placement only changes speed, never results.
-    const int total = n_tiles * S;
-    const int b = blockIdx.x;
-    const int q8 = total >> 3, r8 = total & 7, xcd = b & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-    const int s = L / n_tiles;
-    const int li = L - s * n_tiles;
-    const int tile = order != nullptr ? order[li] : li;
-    const WgradTile tt = wgrad_tile<BATCH, OUT == kOutBF16 ? 2 : 4>(mods, tile_tab, tile);
+    const WgradWork w = wgrad_work<false>(n_tiles, S, order);
+    const int tile = w.tile, s = w.s;
+    const WgradTile<uint16_t> tt = wgrad_tile<BATCH, OUT == kOutBF16 ? 2 : 4>(mods, tile_tab, tile);
     int64_t t_begin, t_end;
     wgrad_span(s, T, chunk, seq, kps, t_begin, t_end);
     const int nst = (t_end > t_begin) ? (int)((t_end - t_begin + kBK - 1) / kBK) : 0;
@@ -339,27 +387,15 @@ void wgrad_partial_kernel(const WgradModules mods, int64_t T, int64_t chunk, int
 #pragma unroll
         for (int i = 0; i < kChunksPerThread; ++i) {
             const int cid = tid + kWgThreads * i;
-            const uint32_t off = img_off((uint32_t)(cid >> 5), (uint32_t)(cid & 31) * 16u);
+            const uint32_t off = img_off<kRowBytes>((uint32_t)(cid >> 5), (uint32_t)(cid & 31) * 16u);
             *reinterpret_cast<uint4*>(A + off) = ra[i];
             *reinterpret_cast<uint4*>(B + off) = rb[i];
         }
     };
 
     f32x16_t acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    // tr-read lane geometry: group gi = lane>>4 covers feature offset 16*(gi&1) and k offset
-    // 8*(gi>>1); lane 4q+p of the group supplies row q, features 4p..4p+3 (T10).
-    const int gi = lane >> 4;
-    const int q = (lane >> 2) & 3;
-    const int p = lane & 3;
-    const uint32_t feat_byte = 2u * (16u * (gi & 1) + 4u * p);
-    const uint32_t krow = 8u * (gi >> 1) + q;
+    wgrad_zero(acc);
+    const TrLane tl = tr_lane(lane);
 
     if (nst > 0) {
         gload(0);
@@ -377,10 +413,10 @@ void wgrad_partial_kernel(const WgradModules mods, int64_t T, int64_t chunk, int
             bf16x8_t af[4], bfr[2];
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb)
-                af[mb] = tr_frag(A, ks * 16 + krow, 2u * (wm * 128 + mb * 32) + feat_byte);
+                af[mb] = tr_frag<kRowBytes>(A, ks * 16 + tl.krow, 2u * (wm * 128 + mb * 32) + tl.feat_byte);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
-                bfr[nb] = tr_frag(B, ks * 16 + krow, 2u * (wn * 64 + nb * 32) + feat_byte);
+                bfr[nb] = tr_frag<kRowBytes>(B, ks * 16 + tl.krow, 2u * (wn * 64 + nb * 32) + tl.feat_byte);
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
@@ -405,9 +441,7 @@ void wgrad_partial_kernel(const WgradModules mods, int64_t T, int64_t chunk, int
 // the image is applied to each lane's SOURCE address instead (rule 21), so the transposed reads are
 // unchanged. Rows past the chunk end read as zeros through the buffer descriptor's range check.
 // ------------------------------------------------------------------------------------------------
-constexpr int kDmaBK = 32;                                 // rows per stage
-constexpr int kDmaImg = kDmaBK * kRowBytes;                // 16 KiB per operand per stage
-constexpr int kDmaSlotBytes = 2 * kDmaImg;                 // A + B
+constexpr int kDmaBK = 32;                                 // rows per stage (image and slot sizes: WgGeo)
 // ring slots: (SLOTS - 2) stages in flight + 1 computing + 1 WAR margin. 4 slots (128 KiB, 2 stages
 // in flight) is the default: 5 slots (160 KiB, the whole LDS of a gfx950 CU, 3 in flight) measured
 // 1-10 % SLOWER at 4-436 tiles, T = 32768 (profiles/r02_wgrad_ring_depth.jsonl): the kernel is not
@@ -455,23 +489,46 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* base,
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
 }
 
-template <int OUT, int SLOTS, bool BATCH, int FMT = kFmtBF16>
-__global__ __launch_bounds__(kWgThreads, 1)
-void wgrad_dma_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, int64_t seq, int kps, int n_tiles,
-                      const int32_t* __restrict__ tile_tab, const int32_t* __restrict__ order,
-                      float* __restrict__ slab) {
-    static_assert(SLOTS >= 3 && SLOTS <= 5, "ring depth");
-    constexpr int AHEAD = SLOTS - 2;                       // stages in flight beside the one computed
-    __shared__ __attribute__((aligned(16))) uint8_t lds[SLOTS * kDmaSlotBytes];   // one array (T-trap 4a)
+// ------------------------------------------------------------------------------------------------
+// Quarter-tile variant for modules with few tiles (the HBM-bound regime: no two tiles share an
+// operand slice). A 256-thread workgroup owns one 128x128 quarter of a tile for one chunk of T rows
+// (4 waves as 2x2, 64x64 outputs each = 2x2 accumulators of v_mfma_f32_32x32x16_bf16), so a tile
+// splits 4 ways over its OUTPUT before it splits over T: 4x fewer split-K slabs for the same number
+// of workgroups, and two workgroups fit per CU (64 KiB LDS each: a 4-slot ring of 32-row stages of
+// two 32 x 128 bf16 half-slices). The four quarters of a (tile, chunk) are consecutive logical ids,
+// so they run on one XCD at the same time and each half-slice is read from HBM once and from L2 by
+// the quarter beside it. Same LDS-DMA / transposed-read machinery and swizzle as wgrad_dma_kernel
+// (one body, wgrad_dma_body, on the geometry below); slabs use the same [tile][S][256][256] layout,
+// so wgrad_reduce_kernel is shared.
+// ------------------------------------------------------------------------------------------------
+constexpr int kQThreads = 256;
+constexpr int kQSlots = 4;
 
-    const int total = n_tiles * S;
-    const int b = blockIdx.x;
-    const int q8 = total >> 3, r8 = total & 7, xcd = b & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-    const int s = L / n_tiles;
-    const int li = L - s * n_tiles;
-    const int tile = order != nullptr ? order[li] : li;
-    const WgradTile tt = wgrad_tile<BATCH, OUT == kOutBF16 ? 2 : 4>(mods, tile_tab, tile);
+// What differs between the full-tile and the quarter-tile LDS-DMA kernels. A DMA instruction always
+// moves 1 KiB and a wave issues two per operand per stage, so a stage is 32 rows either way.
+template <bool QUARTER>
+struct WgGeo {
+    static constexpr int kRowBytes = QUARTER ? 256 : 512;      // image row: 128 or 256 features
+    static constexpr int kMB = QUARTER ? 2 : 4;                // 32-row accumulator blocks per wave along M
+    static constexpr int kWavesN = QUARTER ? 2 : 4;            // waves as 2 (M) x kWavesN (N), 64 columns each
+    static constexpr int kDmaRows = 1024 / kRowBytes;          // image rows per DMA instruction: 2 or 4
+    static constexpr int kRowLanes = 64 / kDmaRows;            // lanes per image row: 32 or 16
+    static constexpr int kImg = kDmaBK * kRowBytes;            // 16 / 8 KiB per operand per stage
+    static constexpr int kSlotBytes = 2 * kImg;                // A + B
+};
+
+template <int OUT, int SLOTS, bool QUARTER, bool BATCH, int FMT>
+__device__ __forceinline__ void wgrad_dma_body(uint8_t* lds, const WgradModules& mods, int64_t T, int64_t chunk, int S,
+                                               int64_t seq, int kps, int n_tiles, const int32_t* __restrict__ tile_tab,
+                                               const int32_t* __restrict__ order, float* __restrict__ slab) {
+    static_assert(SLOTS >= 3 && SLOTS <= 5, "ring depth");
+    using G = WgGeo<QUARTER>;
+    constexpr int AHEAD = SLOTS - 2;                       // stages in flight beside the one computed
+
+    const WgradWork w = wgrad_work<QUARTER>(n_tiles, S, order);
+    const int tile = w.tile, s = w.s;
+    const int qm = w.qd >> 1, qn = w.qd & 1;               // the quarter's origin (0, 0 for a full tile)
+    const WgradTile<uint16_t> tt = wgrad_tile<BATCH, OUT == kOutBF16 ? 2 : 4>(mods, tile_tab, tile);
     const int64_t ldg = tt.ldg, ldx = tt.ldx;
     int64_t t_begin, t_end;
     wgrad_span(s, T, chunk, seq, kps, t_begin, t_end);
@@ -479,23 +536,24 @@ void wgrad_dma_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, 
     const int nst = (rows + kDmaBK - 1) / kDmaBK;
 
     // descriptors over this chunk's rows of the two column slices (host guarantees rows*ld*2 < 2^31)
-    const __amdgpu_buffer_rsrc_t rg = uniform_rsrc(tt.g + t_begin * ldg, (int64_t)rows * ldg * 2);
-    const __amdgpu_buffer_rsrc_t rx = uniform_rsrc(tt.x + t_begin * ldx, (int64_t)rows * ldx * 2);
+    const __amdgpu_buffer_rsrc_t rg = uniform_rsrc(tt.g + t_begin * ldg + qm * 128, (int64_t)rows * ldg * 2);
+    const __amdgpu_buffer_rsrc_t rx = uniform_rsrc(tt.x + t_begin * ldx + qn * 128, (int64_t)rows * ldx * 2);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2;
-    const int wn = wave & 3;
+    const int wm = (unsigned)wave / G::kWavesN;
+    const int wn = (unsigned)wave % G::kWavesN;
 
-    // DMA geometry: wave w fills image rows 4w .. 4w+3 of each operand (two 1 KiB instructions);
-    // lane l of instruction j lands at image row k = 4w + 2j + (l>>5), physical byte 16*(l&31),
-    // which holds logical byte (16*(l&31)) ^ ((k&3) << 6) of that row.
+    // DMA geometry: wave w fills image rows 2R*w .. 2R*w + 2R-1 of each operand (two 1 KiB
+    // instructions of R = kDmaRows rows: 2 x 512 B or 4 x 256 B); lane l of instruction j lands at
+    // image row k = 2R*w + R*j + l / kRowLanes, physical byte 16*(l % kRowLanes), which holds logical
+    // byte (16*(l % kRowLanes)) ^ ((k&3) << 6) of that row.
     int voff_g[2], voff_x[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int k = 4 * wave + 2 * j + (lane >> 5);
-        const int lb = (16 * (lane & 31)) ^ ((k & 3) << 6);
+        const int k = 2 * G::kDmaRows * wave + G::kDmaRows * j + lane / G::kRowLanes;
+        const int lb = (16 * (lane % G::kRowLanes)) ^ ((k & 3) << 6);
         voff_g[j] = (int)(k * ldg * 2) + lb;
         voff_x[j] = (int)(k * ldx * 2) + lb;
     }
@@ -503,28 +561,18 @@ void wgrad_dma_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, 
 
     const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr(lds));
     auto issue = [&](int st) {
-        const uint32_t slot = lds0 + (uint32_t)((st % SLOTS) * kDmaSlotBytes);
+        const uint32_t slot = lds0 + (uint32_t)((st % SLOTS) * G::kSlotBytes);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const uint32_t row0 = (uint32_t)(4 * wave + 2 * j) * kRowBytes;
+            const uint32_t row0 = (uint32_t)(2 * G::kDmaRows * wave + G::kDmaRows * j) * G::kRowBytes;
             dma16(rg, __builtin_amdgcn_readfirstlane(slot + row0), voff_g[j] + st * step_g);
-            dma16(rx, __builtin_amdgcn_readfirstlane(slot + kDmaImg + row0), voff_x[j] + st * step_x);
+            dma16(rx, __builtin_amdgcn_readfirstlane(slot + G::kImg + row0), voff_x[j] + st * step_x);
         }
     };
 
-    f32x16_t acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int gi = lane >> 4;
-    const int q = (lane >> 2) & 3;
-    const int p = lane & 3;
-    const uint32_t feat_byte = 2u * (16u * (gi & 1) + 4u * p);
-    const uint32_t krow = 8u * (gi >> 1) + q;
+    f32x16_t acc[G::kMB][2];
+    wgrad_zero(acc);
+    const TrLane tl = tr_lane(lane);
 
 #pragma unroll
     for (int i = 0; i < AHEAD; ++i)
@@ -540,56 +588,40 @@ void wgrad_dma_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, 
         }
         __builtin_amdgcn_s_barrier();                              // every wave's DMA for stage st landed
         __builtin_amdgcn_sched_barrier(0);
-        const uint8_t* A = lds + (st % SLOTS) * kDmaSlotBytes;
-        const uint8_t* B = A + kDmaImg;
+        const uint8_t* A = lds + (st % SLOTS) * G::kSlotBytes;
+        const uint8_t* B = A + G::kImg;
+        // a plain loop on purpose: as a lambda the k-step measured 1.7 % slower (profiles/README.md,
+        // r03_wgrad_refactor_ab.jsonl)
 #pragma unroll
         for (int ks = 0; ks < kDmaBK / 16; ++ks) {
-            bf16x8_t af[4], bfr[2];
+            bf16x8_t af[G::kMB], bfr[2];
 #pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
-                af[mb] = tr_frag(A, ks * 16 + krow, 2u * (wm * 128 + mb * 32) + feat_byte);
+            for (int mb = 0; mb < G::kMB; ++mb)
+                af[mb] = tr_frag<G::kRowBytes>(A, ks * 16 + tl.krow, 2u * (wm * 32 * G::kMB + mb * 32) + tl.feat_byte);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
-                bfr[nb] = tr_frag(B, ks * 16 + krow, 2u * (wn * 64 + nb * 32) + feat_byte);
+                bfr[nb] = tr_frag<G::kRowBytes>(B, ks * 16 + tl.krow, 2u * (wn * 64 + nb * 32) + tl.feat_byte);
             // x slice as A, g slice as B: the accumulators hold C^T, whose per-lane runs of 4
             // consecutive columns give wgrad_store_t its vector stores
 #pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
+            for (int mb = 0; mb < G::kMB; ++mb)
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb)
                     acc[mb][nb] = mfma16<FMT>(bfr[nb], af[mb], acc[mb][nb]);
         }
     }
-    wgrad_store_t<OUT, 4, FMT>(acc, (OUT == kOutSlab || OUT == kOutSlabBF16) ? wgrad_dst<OUT>(slab, tile, s, S) : tt.out,
-                          wm * 128, wn * 64, lane, tt.accumulate);
+    wgrad_store_t<OUT, G::kMB, FMT>(acc, (OUT == kOutSlab || OUT == kOutSlabBF16) ? wgrad_dst<OUT>(slab, tile, s, S) : tt.out,
+                                    qm * 128 + wm * 32 * G::kMB, qn * 128 + wn * 64, lane, tt.accumulate);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Quarter-tile variant for modules with few tiles (the HBM-bound regime: no two tiles share an
-// operand slice). A 256-thread workgroup owns one 128x128 quarter of a tile for one chunk of T rows
-// (4 waves as 2x2, 64x64 outputs each = 2x2 accumulators of v_mfma_f32_32x32x16_bf16), so a tile
-// splits 4 ways over its OUTPUT before it splits over T: 4x fewer split-K slabs for the same number
-// of workgroups, and two workgroups fit per CU (64 KiB LDS each: a 4-slot ring of 32-row stages of
-// two 32 x 128 bf16 half-slices). The four quarters of a (tile, chunk) are consecutive logical ids,
-// so they run on one XCD at the same time and each half-slice is read from HBM once and from L2 by
-// the quarter beside it. Same LDS-DMA / transposed-read machinery and swizzle as wgrad_dma_kernel;
-// slabs use the same [tile][S][256][256] layout, so wgrad_reduce_kernel is shared.
-// ------------------------------------------------------------------------------------------------
-constexpr int kQThreads = 256;
-constexpr int kQRowBytes = 128 * 2;                         // 256 B: one half-slice row
-constexpr int kQImg = kDmaBK * kQRowBytes;                  // 8 KiB per operand per stage
-constexpr int kQSlotBytes = 2 * kQImg;
-constexpr int kQSlots = 4;
-
-__device__ __forceinline__ uint32_t qimg_off(uint32_t k, uint32_t byte_in_row) {
-    return k * kQRowBytes + (byte_in_row ^ ((k & 3u) << 6));
-}
-
-__device__ __forceinline__ bf16x8_t qtr_frag(const uint8_t* img, uint32_t k, uint32_t byte_in_row) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(img + qimg_off(k, byte_in_row)));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(img + qimg_off(k + 4, byte_in_row)));
-    const s16x8_t both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8_t, both);
+// The two kernels: each declares its LDS ring as ONE array (T-trap 4a) under its own launch bounds.
+template <int OUT, int SLOTS, bool BATCH, int FMT = kFmtBF16>
+__global__ __launch_bounds__(kWgThreads, 1)
+void wgrad_dma_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, int64_t seq, int kps, int n_tiles,
+                      const int32_t* __restrict__ tile_tab, const int32_t* __restrict__ order,
+                      float* __restrict__ slab) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[SLOTS * WgGeo<false>::kSlotBytes];   // 128 KiB (4 slots)
+    wgrad_dma_body<OUT, SLOTS, false, BATCH, FMT>(lds, mods, T, chunk, S, seq, kps, n_tiles, tile_tab, order, slab);
 }
 
 template <int OUT, int QS, bool BATCH, int FMT = kFmtBF16>
@@ -597,108 +629,8 @@ __global__ __launch_bounds__(kQThreads, 2)
 void wgrad_quarter_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, int64_t seq, int kps, int n_tiles,
                           const int32_t* __restrict__ tile_tab, const int32_t* __restrict__ order,
                           float* __restrict__ slab) {
-    static_assert(QS >= 3 && QS <= 5, "ring depth");
-    constexpr int AHEAD = QS - 2;                          // stages in flight beside the one computed
-    __shared__ __attribute__((aligned(16))) uint8_t lds[QS * kQSlotBytes];          // 64 KiB (4 slots), one array
-
-    // logical id L = (s * n_tiles + i) * 4 + quarter, dealt XCD-contiguously (bijective remap)
-    const int total = n_tiles * S * 4;
-    const int b = blockIdx.x;
-    const int q8 = total >> 3, r8 = total & 7, xcd = b & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-    const int qd = L & 3;
-    const int ts = L >> 2;
-    const int s = ts / n_tiles;
-    const int li = ts - s * n_tiles;
-    const int tile = order != nullptr ? order[li] : li;
-    const int qm = qd >> 1, qn = qd & 1;
-    const WgradTile tt = wgrad_tile<BATCH, OUT == kOutBF16 ? 2 : 4>(mods, tile_tab, tile);
-    const int64_t ldg = tt.ldg, ldx = tt.ldx;
-    int64_t t_begin, t_end;
-    wgrad_span(s, T, chunk, seq, kps, t_begin, t_end);
-    const int rows = (t_end > t_begin) ? (int)(t_end - t_begin) : 0;
-    const int nst = (rows + kDmaBK - 1) / kDmaBK;
-
-    const __amdgpu_buffer_rsrc_t rg = uniform_rsrc(tt.g + t_begin * ldg + qm * 128, (int64_t)rows * ldg * 2);
-    const __amdgpu_buffer_rsrc_t rx = uniform_rsrc(tt.x + t_begin * ldx + qn * 128, (int64_t)rows * ldx * 2);
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1;
-    const int wn = wave & 1;
-
-    // DMA geometry: wave w fills image rows 8w .. 8w+7 of each operand (two 1 KiB instructions of
-    // 4 rows x 256 B); lane l of instruction j lands at row k = 8w + 4j + (l>>4), physical byte
-    // 16*(l&15), which holds logical byte (16*(l&15)) ^ ((k&3) << 6) of that row.
-    int voff_g[2], voff_x[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int k = 8 * wave + 4 * j + (lane >> 4);
-        const int lb = (16 * (lane & 15)) ^ ((k & 3) << 6);
-        voff_g[j] = (int)(k * ldg * 2) + lb;
-        voff_x[j] = (int)(k * ldx * 2) + lb;
-    }
-    const int step_g = (int)(kDmaBK * ldg * 2), step_x = (int)(kDmaBK * ldx * 2);
-
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr(lds));
-    auto issue = [&](int st) {
-        const uint32_t slot = lds0 + (uint32_t)((st % QS) * kQSlotBytes);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint32_t row0 = (uint32_t)(8 * wave + 4 * j) * kQRowBytes;
-            dma16(rg, __builtin_amdgcn_readfirstlane(slot + row0), voff_g[j] + st * step_g);
-            dma16(rx, __builtin_amdgcn_readfirstlane(slot + kQImg + row0), voff_x[j] + st * step_x);
-        }
-    };
-
-    f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int gi = lane >> 4;
-    const int q = (lane >> 2) & 3;
-    const int p = lane & 3;
-    const uint32_t feat_byte = 2u * (16u * (gi & 1) + 4u * p);
-    const uint32_t krow = 8u * (gi >> 1) + q;
-
-#pragma unroll
-    for (int i = 0; i < AHEAD; ++i)
-        if (i < nst) issue(i);
-    for (int st = 0; st < nst; ++st) {
-        // 4 DMA instructions per wave per stage (as wgrad_dma_kernel)
-        if (st + AHEAD < nst) {
-            issue(st + AHEAD);
-            wait_vm_stages(AHEAD);
-        } else {
-            wait_vm_stages(nst - 1 - st);
-        }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        const uint8_t* A = lds + (st % QS) * kQSlotBytes;
-        const uint8_t* B = A + kQImg;
-#pragma unroll
-        for (int ks = 0; ks < kDmaBK / 16; ++ks) {
-            bf16x8_t af[2], bfr[2];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-                af[mb] = qtr_frag(A, ks * 16 + krow, 2u * (wm * 64 + mb * 32) + feat_byte);
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-                bfr[nb] = qtr_frag(B, ks * 16 + krow, 2u * (wn * 64 + nb * 32) + feat_byte);
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-                    acc[mb][nb] = mfma16<FMT>(bfr[nb], af[mb], acc[mb][nb]);
-        }
-    }
-    wgrad_store_t<OUT, 2, FMT>(acc, (OUT == kOutSlab || OUT == kOutSlabBF16) ? wgrad_dst<OUT>(slab, tile, s, S) : tt.out,
-                          qm * 128 + wm * 64, qn * 128 + wn * 64, lane, tt.accumulate);
+    __shared__ __attribute__((aligned(16))) uint8_t lds[QS * WgGeo<true>::kSlotBytes];      // 64 KiB (4 slots)
+    wgrad_dma_body<OUT, QS, true, BATCH, FMT>(lds, mods, T, chunk, S, seq, kps, n_tiles, tile_tab, order, slab);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -721,26 +653,13 @@ __global__ __launch_bounds__(kF32Threads, 2)
 void wgrad_f32_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, int64_t seq, int kps, int n_tiles,
                       const int32_t* __restrict__ tile_tab, const int32_t* __restrict__ order,
                       float* __restrict__ slab) {
-    const int total = n_tiles * S * 4;
-    const int b = blockIdx.x;
-    const int q8 = total >> 3, r8 = total & 7, xcd = b & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-    const int qd = L & 3;
-    const int ts = L >> 2;
-    const int s = ts / n_tiles;
-    const int li = ts - s * n_tiles;
-    const int tile = order != nullptr ? order[li] : li;
-    const int qm = qd >> 1, qn = qd & 1;
-    int mi = 0, r, c, ti;
-    if (BATCH) {
-        mi = tile_tab[4 * tile]; r = tile_tab[4 * tile + 1]; c = tile_tab[4 * tile + 2]; ti = tile_tab[4 * tile + 3];
-    } else {
-        r = tile_tab[2 * tile]; c = tile_tab[2 * tile + 1]; ti = tile;
-    }
-    const smt_wgrad_module& m = mods.m[mi];
-    const int64_t ldg = m.ld_grad_out, ldx = m.ld_x;
-    const float* gb = static_cast<const float*>(m.grad_out) + (int64_t)r * kTile;
-    const float* xb = static_cast<const float*>(m.x) + (int64_t)c * m.x_block_stride;
+    const WgradWork w = wgrad_work<true>(n_tiles, S, order);
+    const int tile = w.tile, s = w.s;
+    const int qm = w.qd >> 1, qn = w.qd & 1;
+    const WgradTile<float> tt = wgrad_tile<BATCH, 4, float>(mods, tile_tab, tile);
+    const int64_t ldg = tt.ldg, ldx = tt.ldx;
+    const float* gb = tt.g;
+    const float* xb = tt.x;
     int64_t t_begin, t_end;
     wgrad_span(s, T, chunk, seq, kps, t_begin, t_end);
 
@@ -752,12 +671,7 @@ void wgrad_f32_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, 
     const int kr = lane >> 5, cl = lane & 31;
 
     f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    wgrad_zero(acc);
 
     typedef float Frags[kF32Unroll][2];
     auto load = [&](Frags& ga, Frags& xa, int64_t t0) {    // kF32Unroll row pairs from row t0 on
@@ -800,9 +714,8 @@ void wgrad_f32_kernel(const WgradModules mods, int64_t T, int64_t chunk, int S, 
         if (t0 + 2 * kStep < t_end) load(g0, x0, t0 + 2 * kStep);
         compute(g1, x1);
     }
-    void* out = static_cast<uint8_t*>(m.grad_tiles) + (int64_t)ti * kTileElems * 4;
-    wgrad_store_t<OUT, 2, kFmtF32>(acc, OUT == kOutSlab ? wgrad_dst<OUT>(slab, tile, s, S) : out, m0, n0, lane,
-                                   m.accumulate);
+    wgrad_store_t<OUT, 2, kFmtF32>(acc, OUT == kOutSlab ? wgrad_dst<OUT>(slab, tile, s, S) : tt.out, m0, n0, lane,
+                                   tt.accumulate);
 }
 
 // Sum the S partial slabs of one tile in order s = 0..S-1 (deterministic) and write the tile (this
@@ -886,27 +799,16 @@ void wgrad_reduce_kernel(const float* __restrict__ slab, int S, int kps, void* _
                                accumulate);
 }
 
-// the same over an MX batch
-template <bool OUT_F32>
+// the same over a batch (MODS: WgradModules or WgradMxModules): each tile's output and accumulate
+// flag from its module
+template <bool OUT_F32, bool SLAB16 = false, int FMT = kFmtBF16, typename MODS = WgradModules>
 __global__ __launch_bounds__(256)
-void wgrad_reduce_mx_batch_kernel(const float* __restrict__ slab, int S, const WgradMxModules mods,
-                                  const int32_t* __restrict__ tile_tab) {
-    const int tile = blockIdx.x >> 6;
-    const int m = tile_tab[4 * tile];
-    const int ti = tile_tab[4 * tile + 3];
-    wgrad_reduce_tile<OUT_F32>(slab, S, 0, tile,
-                               static_cast<uint8_t*>(mods.m[m].grad_tiles) + (int64_t)ti * kTileElems * (OUT_F32 ? 4 : 2),
-                               mods.m[m].accumulate);
-}
-
-// the same over a batch: each tile's output and accumulate flag from its module (wgrad_tile)
-template <bool OUT_F32, bool SLAB16 = false, int FMT = kFmtBF16>
-__global__ __launch_bounds__(256)
-void wgrad_reduce_batch_kernel(const float* __restrict__ slab, int S, int kps, const WgradModules mods,
+void wgrad_reduce_batch_kernel(const float* __restrict__ slab, int S, int kps, const MODS mods,
                                const int32_t* __restrict__ tile_tab) {
     const int tile = blockIdx.x >> 6;
-    const WgradTile tt = wgrad_tile<true, OUT_F32 ? 4 : 2>(mods, tile_tab, tile);
-    wgrad_reduce_tile<OUT_F32, SLAB16, FMT>(slab, S, kps, tile, tt.out, tt.accumulate);
+    const WgradTabRow row = wgrad_tab_row<true>(tile_tab, tile);
+    wgrad_reduce_tile<OUT_F32, SLAB16, FMT>(slab, S, MODS::kSeqRounding ? kps : 0, tile,
+                                            wgrad_out<OUT_F32 ? 4 : 2>(mods.m[row.mi], row.ti), mods.m[row.mi].accumulate);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -999,9 +901,8 @@ void mx_quant_cols_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t T
 // Stages stream through a 4-slot LDS-DMA ring (2 stages in flight, counted vmcnt, raw s_barrier)
 // exactly as wgrad_dma_kernel; slabs / epilogue / reduce are shared with it.
 constexpr int kMxBK = 64;                                   // tokens per stage = one MFMA K step
-constexpr int kMxImg = kTile * kMxBK;                       // 16 KiB per operand per stage
-constexpr int kMxSlotBytes = 2 * kMxImg + 2 * 2 * kTile;    // + 2 k-blocks x 256 exponents per operand
-constexpr int kMxSlots = 4;
+constexpr int kMxImg = kTile * kMxBK;                       // 16 KiB: one 64-token panel of a block
+constexpr int kMxSlots = 4;                                 // (image and slot sizes: WgMxGeo)
 
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) uint4 lds_u4_t;
@@ -1050,37 +951,48 @@ struct WgradMxTile {
 template <bool BATCH, int OUT_BYTES>
 __device__ __forceinline__ WgradMxTile wgrad_mx_tile(const WgradMxModules& mods, const int32_t* __restrict__ tab,
                                                      int tile, int64_t ldq) {
-    int mi = 0, r, c, ti;
-    if (BATCH) {
-        mi = tab[4 * tile]; r = tab[4 * tile + 1]; c = tab[4 * tile + 2]; ti = tab[4 * tile + 3];
-    } else {
-        r = tab[2 * tile]; c = tab[2 * tile + 1]; ti = tile;
-    }
-    const smt_wgrad_mx_module& m = mods.m[mi];
+    const WgradTabRow row = wgrad_tab_row<BATCH>(tab, tile);
+    const smt_wgrad_mx_module& m = mods.m[row.mi];
     const int64_t blk_bytes = (int64_t)kTile * ldq, sc_bytes = (ldq >> 5) * kTile;
     WgradMxTile t;
-    t.qa = static_cast<const uint8_t*>(m.qg) + r * blk_bytes;
-    t.sa = static_cast<const uint8_t*>(m.sg) + r * sc_bytes;
-    t.qb = static_cast<const uint8_t*>(m.qx) + c * blk_bytes;
-    t.sb = static_cast<const uint8_t*>(m.sx) + c * sc_bytes;
-    t.out = static_cast<uint8_t*>(m.grad_tiles) + (int64_t)ti * kTileElems * OUT_BYTES;
+    t.qa = static_cast<const uint8_t*>(m.qg) + row.r * blk_bytes;
+    t.sa = static_cast<const uint8_t*>(m.sg) + row.r * sc_bytes;
+    t.qb = static_cast<const uint8_t*>(m.qx) + row.c * blk_bytes;
+    t.sb = static_cast<const uint8_t*>(m.sx) + row.c * sc_bytes;
+    t.out = wgrad_out<OUT_BYTES>(m, row.ti);
     t.accumulate = m.accumulate;
     return t;
 }
 
-template <int OUT, bool BATCH>
-__global__ __launch_bounds__(kWgThreads, 1)
-void wgrad_mx_kernel(const WgradMxModules mods, int64_t ldq, int64_t chunk, int S, int n_tiles,
-                     const int32_t* __restrict__ tile_tab, const int32_t* __restrict__ order, float* __restrict__ slab) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kMxSlots * kMxSlotBytes];   // 132 KiB, one array
+// Quarter-tile MX variant for modules with few tiles (the fill-bound regime, as wgrad_quarter_kernel):
+// 256 threads (4 waves as 2x2, 64x64 outputs each = 2x2 accumulators), one 128x128 quarter of a tile
+// per workgroup, 4-slot ring of 64-token stages of two [128 rows][64 B] images + 2 x 256 B of
+// exponents (66 KiB: two workgroups per CU). Logical ids, schedule, slabs and epilogue as
+// wgrad_quarter_kernel; fragment / scale maps as wgrad_mx_kernel: one body, wgrad_mx_body.
+//
+// What differs between the two. A slot is [A image][B image][A exponents][B exponents]; an operand's
+// exponents are [2 k-blocks][kRows] bytes, moved by kScWaves waves with one 256-B dma4 each: wave w
+// < kScWaves those of A, the next kScWaves those of B, the rest none.
+template <bool QUARTER>
+struct WgMxGeo {
+    static constexpr int kRows = QUARTER ? 128 : 256;          // rows (features) per operand image
+    static constexpr int kMB = QUARTER ? 2 : 4;
+    static constexpr int kWavesN = QUARTER ? 2 : 4;            // waves as 2 (M) x kWavesN (N), 64 columns each
+    static constexpr int kImg = kRows * kMxBK;                 // 16 / 8 KiB per operand per stage
+    static constexpr int kScBytes = 2 * kRows;                 // exponent bytes per operand per slot
+    static constexpr int kScWaves = kScBytes / 256;            // 2 (one k-block each) or 1 (both k-blocks)
+    static constexpr int kSlotBytes = 2 * kImg + 2 * kScBytes;
+};
+static_assert(WgMxGeo<false>::kImg == kMxImg, "a full-tile image is one 64-token panel of the block");
 
-    const int total = n_tiles * S;
-    const int b = blockIdx.x;
-    const int q8 = total >> 3, r8 = total & 7, xcd = b & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-    const int s = L / n_tiles;
-    const int li = L - s * n_tiles;
-    const int tile = order != nullptr ? order[li] : li;
+template <int OUT, bool QUARTER, bool BATCH>
+__device__ __forceinline__ void wgrad_mx_body(uint8_t* lds, const WgradMxModules& mods, int64_t ldq, int64_t chunk, int S,
+                                              int n_tiles, const int32_t* __restrict__ tile_tab,
+                                              const int32_t* __restrict__ order, float* __restrict__ slab) {
+    using G = WgMxGeo<QUARTER>;
+    const WgradWork w = wgrad_work<QUARTER>(n_tiles, S, order);
+    const int tile = w.tile, s = w.s;
+    const int qm = w.qd >> 1, qn = w.qd & 1;               // the quarter's origin (0, 0 for a full tile)
     const WgradMxTile tt = wgrad_mx_tile<BATCH, OUT == kOutBF16 ? 2 : 4>(mods, tile_tab, tile, ldq);
     const int64_t t_begin = (int64_t)s * chunk;
     const int64_t t_end = (t_begin + chunk < ldq) ? (t_begin + chunk) : ldq;
@@ -1088,16 +1000,19 @@ void wgrad_mx_kernel(const WgradMxModules mods, int64_t ldq, int64_t chunk, int 
 
     const int64_t blk_bytes = (int64_t)kTile * ldq;       // = (ldq / 64) panels of 16 KiB
     const int64_t sc_bytes = (ldq >> 5) * kTile;
-    const __amdgpu_buffer_rsrc_t rqa = uniform_rsrc(tt.qa + t_begin * kTile, blk_bytes - t_begin * kTile);
-    const __amdgpu_buffer_rsrc_t rqb = uniform_rsrc(tt.qb + t_begin * kTile, blk_bytes - t_begin * kTile);
+    // from this chunk's first panel on, and there from the quarter's 128 rows of the A / B blocks
+    const __amdgpu_buffer_rsrc_t rqa = uniform_rsrc(tt.qa + t_begin * kTile + qm * 128 * kMxBK,
+                                                    blk_bytes - t_begin * kTile - qm * 128 * kMxBK);
+    const __amdgpu_buffer_rsrc_t rqb = uniform_rsrc(tt.qb + t_begin * kTile + qn * 128 * kMxBK,
+                                                    blk_bytes - t_begin * kTile - qn * 128 * kMxBK);
     const __amdgpu_buffer_rsrc_t rsa = uniform_rsrc(tt.sa + (t_begin >> 5) * kTile, sc_bytes - (t_begin >> 5) * kTile);
     const __amdgpu_buffer_rsrc_t rsb = uniform_rsrc(tt.sb + (t_begin >> 5) * kTile, sc_bytes - (t_begin >> 5) * kTile);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2;
-    const int wn = wave & 3;
+    const int wm = (unsigned)wave / G::kWavesN;
+    const int wn = (unsigned)wave % G::kWavesN;
 
     // DMA geometry: instruction j of wave w fills image rows 16*(2w+j) .. +15 (1 KiB, contiguous in the
     // 64-token panel of the block); lane l lands at row 16*(2w+j) + (l>>2), physical chunk l&3, which
@@ -1108,33 +1023,32 @@ void wgrad_mx_kernel(const WgradMxModules mods, int64_t ldq, int64_t chunk, int 
         const int row = 16 * (2 * wave + j) + (lane >> 2);
         voff[j] = row * kMxBK + ((((lane & 3) ^ ((row >> 2) & 3))) << 4);
     }
-    // exponents: waves 0-3 each move one 256-B k-block row (A kb0, A kb1, B kb0, B kb1) per stage
-    const int sc_kb = wave & 1;
-    const int sc_voff = sc_kb * kTile + 4 * lane;
-    const int per_stage = wave < 4 ? 5 : 4;                 // DMA instructions per stage of this wave
+    // exponents: this wave's dma4 (if any) fills bytes sc_lds .. sc_lds + 255 of its operand's
+    // [2][kRows] exponents; lane l's 4 bytes are features f .. f+3 of k-block 2*st + kb. Full tile:
+    // waves 0-3 each move one 256-B k-block row (A kb0, A kb1, B kb0, B kb1); quarter: wave 0 moves
+    // A's and wave 1 B's, lanes 0-31 the quarter's 128 B of k-block 2*st, lanes 32-63 those of 2*st+1.
+    const int sc_lds = ((unsigned)wave % G::kScWaves) * 256;
+    const int sc_kb = (sc_lds + 4 * lane) / G::kRows, sc_f = (sc_lds + 4 * lane) % G::kRows;
+    const int sc_voff = sc_kb * kTile + (wave < G::kScWaves ? qm : qn) * 128 + sc_f;
+    const int per_stage = wave < 2 * G::kScWaves ? 5 : 4;   // DMA instructions per stage of this wave
 
     const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr(lds));
     auto issue = [&](int st) {
-        const uint32_t slot = lds0 + (uint32_t)((st % kMxSlots) * kMxSlotBytes);
+        const uint32_t slot = lds0 + (uint32_t)((st % kMxSlots) * G::kSlotBytes);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const uint32_t row0 = (uint32_t)(2 * wave + j) * 1024u;
             dma16(rqa, __builtin_amdgcn_readfirstlane(slot + row0), voff[j] + st * kMxImg);
-            dma16(rqb, __builtin_amdgcn_readfirstlane(slot + kMxImg + row0), voff[j] + st * kMxImg);
+            dma16(rqb, __builtin_amdgcn_readfirstlane(slot + G::kImg + row0), voff[j] + st * kMxImg);
         }
-        if (wave < 2)
-            dma4(rsa, __builtin_amdgcn_readfirstlane(slot + 2 * kMxImg + sc_kb * kTile), sc_voff + st * 2 * kTile);
-        else if (wave < 4)
-            dma4(rsb, __builtin_amdgcn_readfirstlane(slot + 2 * kMxImg + 2 * kTile + sc_kb * kTile), sc_voff + st * 2 * kTile);
+        if (wave < G::kScWaves)
+            dma4(rsa, __builtin_amdgcn_readfirstlane(slot + 2 * G::kImg + sc_lds), sc_voff + st * 2 * kTile);
+        else if (wave < 2 * G::kScWaves)
+            dma4(rsb, __builtin_amdgcn_readfirstlane(slot + 2 * G::kImg + G::kScBytes + sc_lds), sc_voff + st * 2 * kTile);
     };
 
-    f32x16_t acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    f32x16_t acc[G::kMB][2];
+    wgrad_zero(acc);
 
     const int r32 = lane & 31;
     const int h = lane >> 5;
@@ -1151,15 +1065,15 @@ void wgrad_mx_kernel(const WgradMxModules mods, int64_t ldq, int64_t chunk, int 
         }
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        const uint8_t* A = lds + (st % kMxSlots) * kMxSlotBytes;
-        const uint8_t* B = A + kMxImg;
-        const uint8_t* SA = A + 2 * kMxImg + h * kTile;     // this lane's k-block of the stage
-        const uint8_t* SB = SA + 2 * kTile;
-        i32x8_t af[4], bfr[2];
-        int as[4], bs[2];
+        const uint8_t* A = lds + (st % kMxSlots) * G::kSlotBytes;
+        const uint8_t* B = A + G::kImg;
+        const uint8_t* SA = A + 2 * G::kImg + h * G::kRows;     // this lane's k-block of the stage
+        const uint8_t* SB = SA + G::kScBytes;
+        i32x8_t af[G::kMB], bfr[2];
+        int as[G::kMB], bs[2];
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-            const int row = wm * 128 + mb * 32 + r32;
+        for (int mb = 0; mb < G::kMB; ++mb) {
+            const int row = wm * 32 * G::kMB + mb * 32 + r32;
             af[mb] = mx_frag(A, row, h);
             as[mb] = SA[row];
         }
@@ -1170,140 +1084,32 @@ void wgrad_mx_kernel(const WgradMxModules mods, int64_t ldq, int64_t chunk, int 
             bs[nb] = SB[col];
         }
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
+        for (int mb = 0; mb < G::kMB; ++mb)
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
                 acc[mb][nb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bfr[nb], af[mb], acc[mb][nb],
                                                                                0, 0, 0, bs[nb], 0, as[mb]);
     }
-    wgrad_store_t<OUT, 4>(acc, (OUT == kOutSlab || OUT == kOutSlabBF16) ? wgrad_dst<OUT>(slab, tile, s, S) : tt.out,
-                          wm * 128, wn * 64, lane, tt.accumulate);
+    wgrad_store_t<OUT, G::kMB>(acc, (OUT == kOutSlab || OUT == kOutSlabBF16) ? wgrad_dst<OUT>(slab, tile, s, S) : tt.out,
+                               qm * 128 + wm * 32 * G::kMB, qn * 128 + wn * 64, lane, tt.accumulate);
 }
 
-// Quarter-tile MX variant for modules with few tiles (the fill-bound regime, as wgrad_quarter_kernel):
-// 256 threads (4 waves as 2x2, 64x64 outputs each = 2x2 accumulators), one 128x128 quarter of a tile
-// per workgroup, 4-slot ring of 64-token stages of two [128 rows][64 B] images + 2 x 256 B of
-// exponents (66 KiB: two workgroups per CU). Logical ids, schedule, slabs and epilogue as
-// wgrad_quarter_kernel; fragment / scale maps as wgrad_mx_kernel.
-constexpr int kMxQImg = 128 * kMxBK;                        // 8 KiB per operand per stage
-constexpr int kMxQSlotBytes = 2 * kMxQImg + 2 * 256;
+// The two kernels: each declares its LDS ring as ONE array under its own launch bounds.
+template <int OUT, bool BATCH>
+__global__ __launch_bounds__(kWgThreads, 1)
+void wgrad_mx_kernel(const WgradMxModules mods, int64_t ldq, int64_t chunk, int S, int n_tiles,
+                     const int32_t* __restrict__ tile_tab, const int32_t* __restrict__ order, float* __restrict__ slab) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kMxSlots * WgMxGeo<false>::kSlotBytes];   // 132 KiB
+    wgrad_mx_body<OUT, false, BATCH>(lds, mods, ldq, chunk, S, n_tiles, tile_tab, order, slab);
+}
 
 template <int OUT, bool BATCH>
 __global__ __launch_bounds__(kQThreads, 2)
 void wgrad_mx_quarter_kernel(const WgradMxModules mods, int64_t ldq, int64_t chunk, int S, int n_tiles,
                              const int32_t* __restrict__ tile_tab, const int32_t* __restrict__ order,
                              float* __restrict__ slab) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kMxSlots * kMxQSlotBytes];  // 66 KiB, one array
-
-    const int total = n_tiles * S * 4;
-    const int b = blockIdx.x;
-    const int q8 = total >> 3, r8 = total & 7, xcd = b & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-    const int qd = L & 3;
-    const int ts = L >> 2;
-    const int s = ts / n_tiles;
-    const int li = ts - s * n_tiles;
-    const int tile = order != nullptr ? order[li] : li;
-    const int qm = qd >> 1, qn = qd & 1;
-    const WgradMxTile tt = wgrad_mx_tile<BATCH, OUT == kOutBF16 ? 2 : 4>(mods, tile_tab, tile, ldq);
-    const int64_t t_begin = (int64_t)s * chunk;
-    const int64_t t_end = (t_begin + chunk < ldq) ? (t_begin + chunk) : ldq;
-    const int nst = (t_end > t_begin) ? (int)((t_end - t_begin) / kMxBK) : 0;
-
-    const int64_t blk_bytes = (int64_t)kTile * ldq;
-    const int64_t sc_bytes = (ldq >> 5) * kTile;
-    // this quarter's 128 rows of the A / B blocks
-    const __amdgpu_buffer_rsrc_t rqa = uniform_rsrc(tt.qa + t_begin * kTile + qm * 128 * kMxBK,
-                                                    blk_bytes - t_begin * kTile - qm * 128 * kMxBK);
-    const __amdgpu_buffer_rsrc_t rqb = uniform_rsrc(tt.qb + t_begin * kTile + qn * 128 * kMxBK,
-                                                    blk_bytes - t_begin * kTile - qn * 128 * kMxBK);
-    const __amdgpu_buffer_rsrc_t rsa = uniform_rsrc(tt.sa + (t_begin >> 5) * kTile, sc_bytes - (t_begin >> 5) * kTile);
-    const __amdgpu_buffer_rsrc_t rsb = uniform_rsrc(tt.sb + (t_begin >> 5) * kTile, sc_bytes - (t_begin >> 5) * kTile);
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1;
-    const int wn = wave & 1;
-
-    // image DMA: instruction j of wave w fills rows 16*(2w+j) .. +15 of each 128-row image (1 KiB
-    // contiguous in the panel layout)
-    int voff[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int row = 16 * (2 * wave + j) + (lane >> 2);
-        voff[j] = row * kMxBK + ((((lane & 3) ^ ((row >> 2) & 3))) << 4);
-    }
-    // exponents: wave 0 moves A's, wave 1 B's: lanes 0-31 the quarter's 128 B of k-block 2st,
-    // lanes 32-63 those of k-block 2st+1
-    const int sc_voff = (lane >> 5) * kTile + (wave == 0 ? qm : qn) * 128 + 4 * (lane & 31);
-    const int per_stage = wave < 2 ? 5 : 4;
-
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr(lds));
-    auto issue = [&](int st) {
-        const uint32_t slot = lds0 + (uint32_t)((st % kMxSlots) * kMxQSlotBytes);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint32_t row0 = (uint32_t)(2 * wave + j) * 1024u;
-            dma16(rqa, __builtin_amdgcn_readfirstlane(slot + row0), voff[j] + st * kMxImg);
-            dma16(rqb, __builtin_amdgcn_readfirstlane(slot + kMxQImg + row0), voff[j] + st * kMxImg);
-        }
-        if (wave == 0)
-            dma4(rsa, __builtin_amdgcn_readfirstlane(slot + 2 * kMxQImg), sc_voff + st * 2 * kTile);
-        else if (wave == 1)
-            dma4(rsb, __builtin_amdgcn_readfirstlane(slot + 2 * kMxQImg + 256), sc_voff + st * 2 * kTile);
-    };
-
-    f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int r32 = lane & 31;
-    const int h = lane >> 5;
-    if (nst > 0) issue(0);
-    if (nst > 1) issue(1);
-    for (int st = 0; st < nst; ++st) {
-        if (st + 2 < nst) {
-            issue(st + 2);
-            wait_vm_n(2 * per_stage);
-        } else if (st + 1 < nst) {
-            wait_vm_n(per_stage);
-        } else {
-            wait_vm_n(0);
-        }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        const uint8_t* A = lds + (st % kMxSlots) * kMxQSlotBytes;
-        const uint8_t* B = A + kMxQImg;
-        const uint8_t* SA = A + 2 * kMxQImg + h * 128;     // this lane's k-block of the stage
-        const uint8_t* SB = SA + 256;
-        i32x8_t af[2], bfr[2];
-        int as[2], bs[2];
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-            const int row = wm * 64 + mb * 32 + r32;
-            af[mb] = mx_frag(A, row, h);
-            as[mb] = SA[row];
-        }
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const int col = wn * 64 + nb * 32 + r32;
-            bfr[nb] = mx_frag(B, col, h);
-            bs[nb] = SB[col];
-        }
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-                acc[mb][nb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bfr[nb], af[mb], acc[mb][nb],
-                                                                               0, 0, 0, bs[nb], 0, as[mb]);
-    }
-    wgrad_store_t<OUT, 2>(acc, (OUT == kOutSlab || OUT == kOutSlabBF16) ? wgrad_dst<OUT>(slab, tile, s, S) : tt.out,
-                          qm * 128 + wm * 64, qn * 128 + wn * 64, lane, tt.accumulate);
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kMxSlots * WgMxGeo<true>::kSlotBytes];    // 66 KiB
+    wgrad_mx_body<OUT, true, BATCH>(lds, mods, ldq, chunk, S, n_tiles, tile_tab, order, slab);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2156,6 +1962,54 @@ size_t smt_wgrad_workspace_bytes(int64_t T, int32_t n_tiles) {
 
 namespace {
 
+// The launchers' shared tails (16-bit / fp32 and MX). `fn`: the entry point's name in the messages.
+
+// the n_tiles x S fp32 partial slabs, taken from the caller's workspace
+int wgrad_slab(const char* fn, int32_t n_tiles, int S, void* workspace, size_t workspace_bytes, float** slab) {
+    const size_t need = (size_t)n_tiles * S * kTileElems * sizeof(float);
+    if (!workspace || workspace_bytes < need)
+        return fail(SMT_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
+    if (!aligned16(workspace)) return fail(SMT_E_ALIGN, "%s: workspace not 16-byte aligned", fn);
+    *slab = static_cast<float*>(workspace);
+    return SMT_OK;
+}
+
+// The reduce of a split launch. slab16 (16-bit slabs) only arises under the reference rounding, and
+// fp32 operands only give fp32 tiles: the other instances are never built.
+template <bool BATCH, int FMT, typename MODS>
+int wgrad_reduce_launch(const MODS& mods, const int32_t* tab, int32_t n_tiles, const float* slab, int S, int kps,
+                        bool out_f32, bool slab16, hipStream_t stream) {
+    const dim3 rgrid(n_tiles * 64), rblock(256);
+#define SMT_WGRAD_REDUCE(F32, S16)                                                                                 \
+    do {                                                                                                          \
+        if (BATCH) hipLaunchKernelGGL((wgrad_reduce_batch_kernel<F32, S16, FMT, MODS>), rgrid, rblock, 0, stream,  \
+                                      slab, S, kps, mods, tab);                                                   \
+        else hipLaunchKernelGGL((wgrad_reduce_kernel<F32, S16, FMT>), rgrid, rblock, 0, stream, slab, S, kps,      \
+                                mods.m[0].grad_tiles, mods.m[0].accumulate);                                      \
+    } while (0)
+    if constexpr (FMT == kFmtF32) {
+        SMT_WGRAD_REDUCE(true, false);
+    } else {
+        if constexpr (MODS::kSeqRounding) {
+            if (slab16 && out_f32) SMT_WGRAD_REDUCE(true, true);
+            else if (slab16) SMT_WGRAD_REDUCE(false, true);
+        }
+        if (!slab16 && out_f32) SMT_WGRAD_REDUCE(true, false);
+        else if (!slab16) SMT_WGRAD_REDUCE(false, false);
+    }
+#undef SMT_WGRAD_REDUCE
+    return check_launch("wgrad_reduce_kernel");
+}
+
+// the result over no rows (T == 0 / ldq == 0): zero tiles, or the output as it is when accumulating
+int zero_tiles(const char* fn, void* grad_tiles, int32_t n_tiles, int32_t out_dtype, int32_t accumulate,
+               hipStream_t stream) {
+    if (accumulate) return SMT_OK;
+    const size_t bytes = (size_t)n_tiles * kTileElems * (out_dtype == SMT_DTYPE_FP32 ? 4 : 2);
+    hipError_t e = hipMemsetAsync(grad_tiles, 0, bytes, stream);
+    return e == hipSuccess ? SMT_OK : fail(SMT_E_LAUNCH, "%s: memset: %s", fn, hipGetErrorString(e));
+}
+
 // Launch the tile wgrad of `n_tiles` tiles (one module, or a batch) and, when split, its reduce.
 // max_ld: the largest leading dimension of any operand (the LDS-DMA kernels' 32-bit buffer offsets
 // need chunk * ld * 2 < 2^31, otherwise the register-staged kernel, which addresses with 64 bits).
@@ -2180,11 +2034,8 @@ int wgrad_launch_fmt(const WgradModules& mods, int64_t T, int64_t max_ld, const 
     const bool slab16 = FMT != kFmtF32 && slab16_ok && dma && sp.seq > 0 && sp.kps == 1;
     float* slab = nullptr;
     if (use_slab) {
-        const size_t need = (size_t)n_tiles * sp.S * kTileElems * sizeof(float);
-        if (!workspace || workspace_bytes < need)
-            return fail(SMT_E_WORKSPACE, "smt_tile_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
-        if (!aligned16(workspace)) return fail(SMT_E_ALIGN, "smt_tile_wgrad: workspace not 16-byte aligned");
-        slab = static_cast<float*>(workspace);
+        const int rc = wgrad_slab("smt_tile_wgrad", n_tiles, sp.S, workspace, workspace_bytes, &slab);
+        if (rc) return rc;
     }
     if constexpr (FMT == kFmtF32) {
         const dim3 fgrid(n_tiles * sp.S * 4), fblock(kF32Threads);
@@ -2222,28 +2073,8 @@ int wgrad_launch_fmt(const WgradModules& mods, int64_t T, int64_t max_ld, const 
         const int rc = check_launch("wgrad kernel");
         if (rc) return rc;
     }
-    const dim3 rgrid(n_tiles * 64), rblock(256);
-    const int kps = sp.seq > 0 ? sp.kps : 0;
-#define SMT_WGRAD_REDUCE(F32, S16)                                                                                 \
-    do {                                                                                                          \
-        if (BATCH) hipLaunchKernelGGL((wgrad_reduce_batch_kernel<F32, S16, FMT>), rgrid, rblock, 0, stream, slab,  \
-                                      sp.S, kps, mods, tab);                                                      \
-        else hipLaunchKernelGGL((wgrad_reduce_kernel<F32, S16, FMT>), rgrid, rblock, 0, stream, slab, sp.S, kps,   \
-                                mods.m[0].grad_tiles, mods.m[0].accumulate);                                      \
-    } while (0)
-    if constexpr (FMT == kFmtF32) {
-        SMT_WGRAD_REDUCE(true, false);
-    } else {
-        if (out_dtype == SMT_DTYPE_FP32) {
-            if (slab16) SMT_WGRAD_REDUCE(true, true);
-            else SMT_WGRAD_REDUCE(true, false);
-        } else {
-            if (slab16) SMT_WGRAD_REDUCE(false, true);
-            else SMT_WGRAD_REDUCE(false, false);
-        }
-    }
-#undef SMT_WGRAD_REDUCE
-    return check_launch("wgrad_reduce_kernel");
+    return wgrad_reduce_launch<BATCH, FMT>(mods, tab, n_tiles, slab, sp.S, sp.seq > 0 ? sp.kps : 0,
+                                           out_dtype == SMT_DTYPE_FP32, slab16, stream);
 }
 
 // The operand format from SMT_DTYPE_* (checked by the entry points against out_dtype).
@@ -2298,12 +2129,7 @@ int smt_tile_wgrad(const void* grad_out, int64_t ld_grad_out, const void* x, int
         return fail(SMT_E_INVALID, "smt_tile_wgrad: out_dtype %d not supported", out_dtype);
     if (!tile_rc_dev || !grad_tiles) return fail(SMT_E_INVALID, "smt_tile_wgrad: null tile table or output");
     if (!aligned16(grad_tiles)) return fail(SMT_E_ALIGN, "smt_tile_wgrad: output not 16-byte aligned");
-    if (T == 0) {
-        if (accumulate) return SMT_OK;
-        const size_t bytes = (size_t)n_tiles * kTileElems * (out_dtype == SMT_DTYPE_FP32 ? 4 : 2);
-        hipError_t e = hipMemsetAsync(grad_tiles, 0, bytes, stream);
-        return e == hipSuccess ? SMT_OK : fail(SMT_E_LAUNCH, "smt_tile_wgrad: memset: %s", hipGetErrorString(e));
-    }
+    if (T == 0) return zero_tiles("smt_tile_wgrad", grad_tiles, n_tiles, out_dtype, accumulate, stream);
     if (!grad_out || !x) return fail(SMT_E_INVALID, "smt_tile_wgrad: null operand");
     if (!aligned16(grad_out) || !aligned16(x) || (ld_grad_out & 7) || (ld_x & 7))
         return fail(SMT_E_ALIGN, "smt_tile_wgrad: operands need 16-byte aligned rows (ld %% 8 == 0)");
@@ -2416,11 +2242,8 @@ int wgrad_mx_launch(const WgradMxModules& mods, int64_t ldq, const int32_t* tab,
     const dim3 qgrid(n_tiles * sp.S * 4), qblock(kQThreads);
     float* slab = nullptr;
     if (sp.S > 1) {
-        const size_t need = (size_t)n_tiles * sp.S * kTileElems * sizeof(float);
-        if (!workspace || workspace_bytes < need)
-            return fail(SMT_E_WORKSPACE, "smt_tile_wgrad_mx: workspace %zu < %zu bytes", workspace_bytes, need);
-        if (!aligned16(workspace)) return fail(SMT_E_ALIGN, "smt_tile_wgrad_mx: workspace not 16-byte aligned");
-        slab = static_cast<float*>(workspace);
+        const int rc = wgrad_slab("smt_tile_wgrad_mx", n_tiles, sp.S, workspace, workspace_bytes, &slab);
+        if (rc) return rc;
     }
 #define SMT_WGRAD_MX(OUT)                                                                                       \
     do {                                                                                                        \
@@ -2436,22 +2259,10 @@ int wgrad_mx_launch(const WgradMxModules& mods, int64_t ldq, const int32_t* tab,
     }
     SMT_WGRAD_MX(kOutSlab);
 #undef SMT_WGRAD_MX
-    int rc = check_launch("wgrad_mx_kernel");
+    const int rc = check_launch("wgrad_mx_kernel");
     if (rc) return rc;
-    const dim3 rgrid(n_tiles * 64), rblock(256);
-    if (BATCH) {
-        if (out_dtype == SMT_DTYPE_FP32)
-            hipLaunchKernelGGL(wgrad_reduce_mx_batch_kernel<true>, rgrid, rblock, 0, stream, slab, sp.S, mods, tab);
-        else
-            hipLaunchKernelGGL(wgrad_reduce_mx_batch_kernel<false>, rgrid, rblock, 0, stream, slab, sp.S, mods, tab);
-    } else {
-        const smt_wgrad_mx_module& m = mods.m[0];
-        if (out_dtype == SMT_DTYPE_FP32)
-            hipLaunchKernelGGL(wgrad_reduce_kernel<true>, rgrid, rblock, 0, stream, slab, sp.S, 0, m.grad_tiles, m.accumulate);
-        else
-            hipLaunchKernelGGL(wgrad_reduce_kernel<false>, rgrid, rblock, 0, stream, slab, sp.S, 0, m.grad_tiles, m.accumulate);
-    }
-    return check_launch("wgrad_reduce_kernel");
+    return wgrad_reduce_launch<BATCH, kFmtBF16>(mods, tab, n_tiles, slab, sp.S, 0, out_dtype == SMT_DTYPE_FP32, false,
+                                                stream);
 }
 
 int check_mx_module(const char* fn, const smt_wgrad_mx_module& m) {
@@ -2476,12 +2287,7 @@ int smt_tile_wgrad_mx(const void* qg, const void* sg, const void* qx, const void
         return fail(SMT_E_INVALID, "smt_tile_wgrad_mx: out_dtype %d not supported", out_dtype);
     if (!tile_rc_dev || !grad_tiles) return fail(SMT_E_INVALID, "smt_tile_wgrad_mx: null tile table or output");
     if (!aligned16(grad_tiles)) return fail(SMT_E_ALIGN, "smt_tile_wgrad_mx: output not 16-byte aligned");
-    if (ldq == 0) {
-        if (accumulate) return SMT_OK;
-        const size_t bytes = (size_t)n_tiles * kTileElems * (out_dtype == SMT_DTYPE_FP32 ? 4 : 2);
-        hipError_t e = hipMemsetAsync(grad_tiles, 0, bytes, stream);
-        return e == hipSuccess ? SMT_OK : fail(SMT_E_LAUNCH, "smt_tile_wgrad_mx: memset: %s", hipGetErrorString(e));
-    }
+    if (ldq == 0) return zero_tiles("smt_tile_wgrad_mx", grad_tiles, n_tiles, out_dtype, accumulate, stream);
     if (!qg || !sg || !qx || !sx) return fail(SMT_E_INVALID, "smt_tile_wgrad_mx: null operand");
     if (!aligned16(qg) || !aligned16(qx) || !aligned16(sg) || !aligned16(sx))
         return fail(SMT_E_ALIGN, "smt_tile_wgrad_mx: operands not 16-byte aligned");

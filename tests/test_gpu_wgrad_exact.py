@@ -223,13 +223,15 @@ BATCH_TILES = {
 BLOCK_MAJOR_COLS = [1, 0]                                       # module 2's x: its column blocks in this order
 
 
-@pytest.mark.parametrize("dt", [BF16, FP16], ids=_id)
+@pytest.mark.parametrize("dt", [BF16, FP16, F32], ids=_id)
 @pytest.mark.parametrize("T,seq", [(300, 0), (1100, 0), (300, 100)], ids=["direct", "slabs", "seq-3x100"])
 @pytest.mark.parametrize("total", [8, 11])
 def test_batch_of_three_modules(total, T, seq, dt):
     """One launch over three modules of different widths: module 1 accumulates, module 2 reads the block-major
-    copy of ``colblock_gather``, the tile indices are a non-identity permutation of table order, the table
-    rows are shuffled over the modules and ``order`` is a random permutation. Bit-identical without ``order``."""
+    copy of ``colblock_gather`` (fp32 operands, which it does not take: the same copy by indexing), the tile
+    indices are a non-identity permutation of table order, the table rows are shuffled over the modules and
+    ``order`` is a random permutation. Bit-identical without ``order``. fp32 operands (``wgrad_f32_kernel``
+    on table rows of every module) give fp32 tiles only."""
     module_tiles = BATCH_TILES[total]
     assert sum(len(t) for t in module_tiles) == total and (total <= QUARTER_MAX) == (total == 8)
     if seq:
@@ -243,9 +245,12 @@ def test_batch_of_three_modules(total, T, seq, dt):
         if slot == sorted(slot):
             slot = slot[::-1]
         xd = _rows_view(x)
-        if m == 2:
+        if m == 2 and dt == F32:
+            xd = torch.stack([xd[:, 256 * c:256 * (c + 1)] for c in BLOCK_MAJOR_COLS]).contiguous()
+        elif m == 2:
             xd = _hip.colblock_gather(xd, torch.tensor(BLOCK_MAJOR_COLS, dtype=torch.int32, device=DEV))
-            assert xd.shape == (len(BLOCK_MAJOR_COLS), T, 256)
+        if m == 2:
+            assert xd.shape == (len(BLOCK_MAJOR_COLS), T, 256) and xd.is_contiguous()
         mods.append(dict(g=g, x=x, gd=_rows_view(g), xd=xd, tiles=tiles, slot=slot, acc=(m == 1)))
     rows = []
     for m, md in enumerate(mods):
@@ -253,7 +258,7 @@ def test_batch_of_three_modules(total, T, seq, dt):
             rows.append((m, r, BLOCK_MAJOR_COLS.index(c) if m == 2 else c, md["slot"][i]))
     shuffle = torch.randperm(total, generator=torch.Generator().manual_seed(total)).tolist()
     tab = torch.tensor([rows[i] for i in shuffle], dtype=torch.int32, device=DEV)
-    for out_dt in (dt, F32):
+    for out_dt in ((dt, F32) if dt != F32 else (F32,)):
         results = []
         for order in (_order(total, 9), None):
             outs = []
@@ -318,7 +323,7 @@ def test_mx_against_the_single_rounding_of_the_bf16_operands(n, kind):
 
 @pytest.mark.parametrize("total", [2, 9])
 def test_mx_batch_of_two_modules_with_slabs(total):
-    """Two modules in one launch at the first T that splits (``wgrad_reduce_mx_batch_kernel``), module 1
+    """Two modules in one launch at the first T that splits (``wgrad_reduce_batch_kernel`` on the MX modules), module 1
     accumulating, tile indices reversed, the table rows interleaved, a random ``order``."""
     T, ldq = _mx_first_slab_T(total)
     assert _splits_mx(ldq, total) > 1
