@@ -10,9 +10,11 @@
  * hipBLASLt rowwise-scaled fp8 GEMMs. After every optimizer step the rows / columns that the
  * updated 256x256 tiles touch are re-quantised from the bf16 W (whose tiles the AdamW epilogue wrote).
  *
- * Quantisation (both kernels): scale = amax * fp32(1/448) (1 when amax == 0), q = e4m3_rne(x / scale),
- * with x / scale an IEEE fp32 division, so the bytes equal torch's
- * (x.float() / scale).to(torch.float8_e4m3fn).
+ * Quantisation (every kernel here): scale = amax * fp32(1/448) (1 when amax == 0), q = e4m3_rne(x / scale),
+ * with x / scale the correctly rounded fp32 quotient, so the bytes and scales equal torch's
+ * (x.float() / scale).to(torch.float8_e4m3fn) bit for bit for every finite bf16 input, down to rows of
+ * subnormals and including the sign of a zero. A row (column) that holds an infinity or a NaN is outside
+ * the contract: its bytes and scale are unspecified.
  * Return 0 or a negative code; smt_fp8_last_error() holds the message.
  */
 #ifndef SMT_FP8_H

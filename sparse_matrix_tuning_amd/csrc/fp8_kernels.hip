@@ -7,9 +7,11 @@
 // GEMM. hipBLASLt then runs the rowwise-scaled fp8 GEMMs (2.4-2.9 PF/s on the LLaMA-3-8B shapes
 // against 1.4-1.6 PF/s bf16, profiles/r01_fp8_probe.jsonl).
 //
-// scale = amax * fp32(1/448) (1 when amax == 0); q = e4m3_rne(x / scale), IEEE fp32 division and
-// v_cvt_pk_fp8_f32 (round to nearest even, OCP e4m3 on gfx950), clamped to +-448 first, so the
-// bytes equal torch's (x.float() / scale).to(torch.float8_e4m3fn).
+// scale = amax * fp32(1/448) (1 when amax == 0); q = e4m3_rne(x / scale), the correctly rounded fp32
+// quotient (fp8_math.h) and v_cvt_pk_fp8_f32 (round to nearest even, OCP e4m3 on gfx950), clamped to
+// +-448 first, so the bytes equal torch's (x.float() / scale).to(torch.float8_e4m3fn) for every finite
+// bf16 input: rows of subnormals and -0.0 included (tests/test_gpu_fp8_exact.py). Rows holding an
+// infinity or a NaN are outside the contract.
 
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -92,8 +94,8 @@ void quant_rows_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t rows
     for (int c = lane; c < nch; c += 64) {
         const F8 v = ld8(xr + c * 8);
         uint2 w;
-        w.x = pack4(qv(v.v[0], scale), qv(v.v[1], scale), qv(v.v[2], scale), qv(v.v[3], scale));
-        w.y = pack4(qv(v.v[4], scale), qv(v.v[5], scale), qv(v.v[6], scale), qv(v.v[7], scale));
+        w.x = quant4(v.v[0], v.v[1], v.v[2], v.v[3], scale);
+        w.y = quant4(v.v[4], v.v[5], v.v[6], v.v[7], scale);
         *reinterpret_cast<uint2*>(orow + c * 8) = w;
     }
 }
@@ -136,10 +138,8 @@ void quant_rows_reg_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t 
         if (c < nch) {
             const uint32_t w[4] = {buf[i].x, buf[i].y, buf[i].z, buf[i].w};
             uint2 o;
-            o.x = pack4(qv(bf(w[0] & 0xffffu), scale), qv(bf(w[0] >> 16), scale),
-                        qv(bf(w[1] & 0xffffu), scale), qv(bf(w[1] >> 16), scale));
-            o.y = pack4(qv(bf(w[2] & 0xffffu), scale), qv(bf(w[2] >> 16), scale),
-                        qv(bf(w[3] & 0xffffu), scale), qv(bf(w[3] >> 16), scale));
+            o.x = quant4(bf(w[0] & 0xffffu), bf(w[0] >> 16), bf(w[1] & 0xffffu), bf(w[1] >> 16), scale);
+            o.y = quant4(bf(w[2] & 0xffffu), bf(w[2] >> 16), bf(w[3] & 0xffffu), bf(w[3] >> 16), scale);
             *reinterpret_cast<uint2*>(orow + c * 8) = o;
         }
     }
@@ -187,10 +187,8 @@ void quant_rows_wg_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t r
         if (c < nch) {
             const uint32_t w[4] = {buf[i].x, buf[i].y, buf[i].z, buf[i].w};
             uint2 o;
-            o.x = pack4(qv(bf(w[0] & 0xffffu), scale), qv(bf(w[0] >> 16), scale),
-                        qv(bf(w[1] & 0xffffu), scale), qv(bf(w[1] >> 16), scale));
-            o.y = pack4(qv(bf(w[2] & 0xffffu), scale), qv(bf(w[2] >> 16), scale),
-                        qv(bf(w[3] & 0xffffu), scale), qv(bf(w[3] >> 16), scale));
+            o.x = quant4(bf(w[0] & 0xffffu), bf(w[0] >> 16), bf(w[1] & 0xffffu), bf(w[1] >> 16), scale);
+            o.y = quant4(bf(w[2] & 0xffffu), bf(w[2] >> 16), bf(w[3] & 0xffffu), bf(w[3] >> 16), scale);
             *reinterpret_cast<uint2*>(orow + c * 8) = o;
         }
     }
@@ -252,10 +250,8 @@ void quant_rows_cat_kernel(CatSrcs src, int64_t rows, uint8_t* __restrict__ out,
         if (c < nch) {
             const uint32_t w[4] = {buf[i].x, buf[i].y, buf[i].z, buf[i].w};
             uint2 o;
-            o.x = pack4(qv(bf(w[0] & 0xffffu), scale), qv(bf(w[0] >> 16), scale),
-                        qv(bf(w[1] & 0xffffu), scale), qv(bf(w[1] >> 16), scale));
-            o.y = pack4(qv(bf(w[2] & 0xffffu), scale), qv(bf(w[2] >> 16), scale),
-                        qv(bf(w[3] & 0xffffu), scale), qv(bf(w[3] >> 16), scale));
+            o.x = quant4(bf(w[0] & 0xffffu), bf(w[0] >> 16), bf(w[1] & 0xffffu), bf(w[1] >> 16), scale);
+            o.y = quant4(bf(w[2] & 0xffffu), bf(w[2] >> 16), bf(w[3] & 0xffffu), bf(w[3] >> 16), scale);
             *reinterpret_cast<uint2*>(orow + c * 8) = o;
         }
     }
@@ -337,10 +333,8 @@ void swiglu_bwd_quant_kernel(const uint16_t* __restrict__ g, const uint16_t* __r
                 const uint4 v = half ? duv[i] : dgv[i];
                 const uint32_t w[4] = {v.x, v.y, v.z, v.w};
                 uint2 o;
-                o.x = pack4(qv(bf(w[0] & 0xffffu), scale), qv(bf(w[0] >> 16), scale),
-                            qv(bf(w[1] & 0xffffu), scale), qv(bf(w[1] >> 16), scale));
-                o.y = pack4(qv(bf(w[2] & 0xffffu), scale), qv(bf(w[2] >> 16), scale),
-                            qv(bf(w[3] & 0xffffu), scale), qv(bf(w[3] >> 16), scale));
+                o.x = quant4(bf(w[0] & 0xffffu), bf(w[0] >> 16), bf(w[1] & 0xffffu), bf(w[1] >> 16), scale);
+                o.y = quant4(bf(w[2] & 0xffffu), bf(w[2] >> 16), bf(w[3] & 0xffffu), bf(w[3] >> 16), scale);
                 *reinterpret_cast<uint2*>(orow + (int64_t)half * cols + c * 8) = o;
             }
             if (dg_out) {
@@ -411,10 +405,8 @@ void swiglu_fwd_quant_kernel(const uint16_t* __restrict__ g, const uint16_t* __r
         if (c < nch) {
             const uint32_t w[4] = {hv[i].x, hv[i].y, hv[i].z, hv[i].w};
             uint2 o;
-            o.x = pack4(qv(bf(w[0] & 0xffffu), scale), qv(bf(w[0] >> 16), scale),
-                        qv(bf(w[1] & 0xffffu), scale), qv(bf(w[1] >> 16), scale));
-            o.y = pack4(qv(bf(w[2] & 0xffffu), scale), qv(bf(w[2] >> 16), scale),
-                        qv(bf(w[3] & 0xffffu), scale), qv(bf(w[3] >> 16), scale));
+            o.x = quant4(bf(w[0] & 0xffffu), bf(w[0] >> 16), bf(w[1] & 0xffffu), bf(w[1] >> 16), scale);
+            o.y = quant4(bf(w[2] & 0xffffu), bf(w[2] >> 16), bf(w[3] & 0xffffu), bf(w[3] >> 16), scale);
             *reinterpret_cast<uint2*>(orow + c * 8) = o;
             if (h_out) *reinterpret_cast<uint4*>(h_out + row * ld + (int64_t)c * 8) = hv[i];
         }
@@ -492,8 +484,8 @@ void cols_t_quant_kernel(const uint16_t* __restrict__ w, int64_t ldw, int rows, 
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int rr = q * 16 + k * 4;
-                wd[k] = pack4(qv(bf(slab[rr][tid]), scale), qv(bf(slab[rr + 1][tid]), scale),
-                              qv(bf(slab[rr + 2][tid]), scale), qv(bf(slab[rr + 3][tid]), scale));
+                wd[k] = quant4(bf(slab[rr][tid]), bf(slab[rr + 1][tid]), bf(slab[rr + 2][tid]), bf(slab[rr + 3][tid]),
+                               scale);
             }
             *reinterpret_cast<uint4*>(orow + r0 + q * 16) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
         }

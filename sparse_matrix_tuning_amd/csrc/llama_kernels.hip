@@ -300,8 +300,8 @@ void rmsnorm_fwd_reg_kernel(const uint16_t* __restrict__ x, int64_t ldx, const u
     for (int k = 0; k < CPL; ++k) {
         const int c = lane + 64 * k;
         uint2 o;
-        o.x = pack4(qv(v[k].v[0], scale), qv(v[k].v[1], scale), qv(v[k].v[2], scale), qv(v[k].v[3], scale));
-        o.y = pack4(qv(v[k].v[4], scale), qv(v[k].v[5], scale), qv(v[k].v[6], scale), qv(v[k].v[7], scale));
+        o.x = quant4(v[k].v[0], v[k].v[1], v[k].v[2], v[k].v[3], scale);
+        o.y = quant4(v[k].v[4], v[k].v[5], v[k].v[6], v[k].v[7], scale);
         *reinterpret_cast<uint2*>(q8 + row * ldq + c * 8) = o;
     }
 }
@@ -392,8 +392,8 @@ void rmsnorm_bwd_reg_kernel(const uint16_t* __restrict__ dy, int64_t lddy, const
             const int c = lane + 64 * k;
             const F8 d = RowReg<PACK, F>::get(gr[k]);
             uint2 q;
-            q.x = pack4(qv(d.v[0], scale), qv(d.v[1], scale), qv(d.v[2], scale), qv(d.v[3], scale));
-            q.y = pack4(qv(d.v[4], scale), qv(d.v[5], scale), qv(d.v[6], scale), qv(d.v[7], scale));
+            q.x = quant4(d.v[0], d.v[1], d.v[2], d.v[3], scale);
+            q.y = quant4(d.v[4], d.v[5], d.v[6], d.v[7], scale);
             *reinterpret_cast<uint2*>(q8 + row * ldq + c * 8) = q;
         }
     }
