@@ -1,0 +1,72 @@
+/*
+ * smt_linear.h — C-ABI of the decode linears (csrc/linear_kernels.hip, same library libsmt_hip.so):
+ * y[M, N] = x[M, K] * W[N, K]^T for 1 <= M <= 16 rows, the shape of every dense linear of a decode step
+ * (prompts x beams rows). At these M a GEMM is one read of W with a trivial amount of arithmetic, so the
+ * kernel is a weight stream: W is read once, as it lies in the model (nn.Linear.weight, row-major [N][K],
+ * no repack and no copy), with non-temporal 16-byte loads straight into the A operand of
+ * v_mfma_f32_16x16x32_{bf16,f16}; x is the B operand. fp32 accumulation, one rounding to the dtype at
+ * the store.
+ *
+ * Sizes and alignment: K % 32 == 0, N % 16 == 0; ldx, ldw, ldy multiples of 8 elements with ldx >= K,
+ * ldw >= K, ldy >= N; every pointer 16-byte aligned. K / 32 need not divide by anything.
+ *
+ * Determinism: no atomics, a fixed reduction order, bit-reproducible. One workgroup owns 16 output
+ * features; its SMT_LINEAR_KSPLIT waves take one contiguous K-slice each (a function of K alone) and
+ * their fp32 partials are added in wave order through the LDS. The x row is a COLUMN of the MFMA, and
+ * columns never mix, so a row's output is a function of that row of x and of W alone: not of M, of the
+ * row's index, or of what the other rows hold.
+ *
+ * Memory: rows >= M of x are never read; nothing of y is written outside [0, M) x [0, N).
+ *
+ * No synchronisation between workgroups: no persistent loop, no grid barrier, no spin, no ticket, no
+ * split of K across workgroups. smt_linear_skinny_workspace therefore returns 0 for every valid shape
+ * and `workspace` may be NULL; both exist so that a later split-K form (fp32 partials plus a second,
+ * ordinary launch) needs no ABI change.
+ *
+ * One launch on `stream`, no allocation, no host synchronisation; launch parameters depend on shapes and
+ * pointers only, so a captured call replays.
+ * Return 0, -1 (invalid argument, before any HIP call), -2 (misaligned pointer or leading dimension,
+ * before any HIP call), -4 (launch failure); smt_linear_last_error() holds the message.
+ */
+#ifndef SMT_LINEAR_H
+#define SMT_LINEAR_H
+
+#include <stdint.h>
+#include <hip/hip_runtime_api.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SMT_LINEAR_MAX_M 16
+#define SMT_LINEAR_MAX_OUT 3
+#define SMT_LINEAR_KSPLIT 8       /* fp32 partials combined per output element, in a fixed order */
+
+typedef struct {
+    const void* w;                /* [N][ldw] of the call's dtype */
+    int64_t ldw;
+    void* y;                      /* [M][ldy] of the call's dtype */
+    int64_t ldy;
+    int32_t N;
+    int32_t reserved;
+} SmtSkinnyOut;
+
+#define SMT_SKINNY_PLAIN 0        /* y_i = x * W_i^T for each of n_out (1..3) outputs: one launch reads x once */
+#define SMT_SKINNY_SWIGLU 1       /* n_out == 2, equal N: outs[0].y = swiglu(x * W_0^T, x * W_1^T); outs[1].y unused.
+                                     Gate and up are each rounded to the dtype first, then the arithmetic of the
+                                     SwiGLU forward of smt_model_ops.h, dtype(silu(g)) * u: bit for bit the chain of
+                                     two PLAIN calls and that kernel. */
+
+const char* smt_linear_last_error(void);
+
+/* Bytes of workspace for smt_linear_skinny with these sizes (0 today); -1 if they are invalid. */
+int64_t smt_linear_skinny_workspace(int32_t M, int32_t K, const SmtSkinnyOut* outs, int32_t n_out, int32_t epilogue);
+
+/* x: [M][ldx] of `dtype` (SMT_DTYPE_BF16 / SMT_DTYPE_FP16 of smt_hip.h). outs: HOST array of n_out entries. */
+int smt_linear_skinny(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t dtype, const SmtSkinnyOut* outs,
+                      int32_t n_out, int32_t epilogue, void* workspace, hipStream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SMT_LINEAR_H */

@@ -19,7 +19,17 @@ three legs are bound by the host (a decode step is about 500 launches at 32 laye
 ``custom_generate=smt_beam_search`` (sparse_matrix_tuning_amd/beam_search.py: the scoring of a token as one
 smt_beam_topk call). The (cache, loop) legs alternate within a round; every line carries ``loop``, and the
 smt legs ``same_tokens_as_transformers_loop`` (the same cache under transformers' loop) and the loop's
-``delegated`` count. ``--repetition-penalty 1.1`` is the reference's setting; ``--caches`` picks the legs."""
+``delegated`` count. ``--repetition-penalty 1.1`` is the reference's setting; ``--caches`` picks the legs.
+
+``--decode-linears [all single nogroup noswiglu ...]`` (default ``all`` when given bare) adds, for every
+``beam_shared_graph`` leg, the same leg on the model patched with ``patch_llama(decode_linears=True)``: the
+decode steps' dense linears on the weight-streaming kernel (``cache`` stays ``beam_shared_graph``, the line's
+``decode_linears`` names the variant: ``all`` = q/k/v as one launch and gate/up/SwiGLU as one, ``single`` =
+neither, ``nogroup`` / ``noswiglu`` = without the one, ``unbounded*`` = the same without the routing's size
+rule, every qualifying launch on the kernel). The routing is put on and taken off between legs
+(``route_decode_linears`` / ``unroute_decode_linears``), outside the timing; the leg without the flag runs
+the modules as ``patch_llama(model)`` leaves them. The ratio line carries
+``seconds_graph_over_<variant>`` per loop."""
 import argparse
 import json
 import os
@@ -32,7 +42,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import MODELS, build_model  # noqa: E402
 from sparse_matrix_tuning_amd import beam_search  # noqa: E402
 from sparse_matrix_tuning_amd.beam_cache import BeamSharedCache  # noqa: E402
+from sparse_matrix_tuning_amd import fused_llama  # noqa: E402
 from sparse_matrix_tuning_amd.fused_llama import DecodeGraph, patch_llama  # noqa: E402
+
+DL_RULE, DL_MAX_K = fused_llama.DECODE_LINEAR_MAX_WEIGHT_ELEMS, fused_llama.DECODE_LINEAR_MAX_K
+# variant: (q/k/v as one launch, gate/up/SwiGLU as one launch, the size rule's limit)
+DL_VARIANTS = {"all": (True, True, DL_RULE), "single": (False, False, DL_RULE), "nogroup": (False, True, DL_RULE),
+               "noswiglu": (True, False, DL_RULE), "unbounded": (True, True, 1 << 62),
+               "unbounded_single": (False, False, 1 << 62), "unbounded_nogroup": (False, True, 1 << 62),
+               "unbounded_noswiglu": (True, False, 1 << 62)}
 
 
 def main():
@@ -47,7 +65,11 @@ def main():
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--caches", nargs="+", default=["dynamic", "static", "beam_shared", "beam_shared_graph"],
                     choices=["dynamic", "static", "beam_shared", "beam_shared_graph"])
+    ap.add_argument("--decode-linears", nargs="*", default=None, choices=sorted(DL_VARIANTS),
+                    help="add beam_shared_graph legs on a model patched with decode_linears=True")
     a = ap.parse_args()
+    if a.decode_linears is not None and not a.decode_linears:
+        a.decode_linears = ["all"]
     if not torch.cuda.is_available():
         raise SystemExit("generate_cache_bench: needs the GPU")
     dev = torch.device("cuda", 0)
@@ -83,12 +105,28 @@ def main():
         extra = {} if a.repetition_penalty == 1.0 else {"repetition_penalty": a.repetition_penalty}
         loops = {"transformers": {}, "smt": {"custom_generate": beam_search.smt_beam_search}}
         leg = lambda cache, loop: cache if loop == "transformers" else f"{cache}+{loop}"
-        kinds = tuple((leg(c, lp), (lambda c=c, lp=lp: {**caches[c](), **loops[lp], **extra}))
-                      for c in a.caches for lp in a.loop)
+        variants = lambda c: [None] + (list(a.decode_linears or ()) if c == "beam_shared_graph" else [])
+        kinds = tuple((leg(c if v is None else f"{c}@{v}", lp), (lambda c=c, lp=lp: {**caches[c](), **loops[lp], **extra}))
+                      for c in a.caches for v in variants(c) for lp in a.loop)
         first = kinds[0][0]
+        variant_of = lambda name: name.split("+")[0].partition("@")[2] or None
+        routed = {"now": None}
 
-        def run(kw):
+        def route(v):
+            """The model patched for variant ``v`` (None: without the decode linears)."""
+            if v != routed["now"]:
+                fused_llama.unroute_decode_linears(model)
+                if v is not None:
+                    fused_llama.route_decode_linears(model)
+                    (fused_llama.DECODE_LINEAR_GROUP, fused_llama.DECODE_LINEAR_SWIGLU,
+                     fused_llama.DECODE_LINEAR_MAX_WEIGHT_ELEMS) = DL_VARIANTS[v]
+                    fused_llama.DECODE_LINEAR_MAX_K = DL_MAX_K if DL_VARIANTS[v][2] == DL_RULE else 1 << 30
+                routed["now"] = v
+
+        def run(kw, v=None):
+            route(v)
             kw = kw()
+            fused_llama.decode_linear_stats.reset()
             beam_search.stats.reset()
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -98,21 +136,26 @@ def main():
             torch.cuda.synchronize()
             return time.perf_counter() - t, out, kw.get("past_key_values")
 
-        outs = {name: run(kw)[1] for name, kw in kinds}    # untimed
+        outs = {name: run(kw, variant_of(name))[1] for name, kw in kinds}    # untimed
         same = {name: bool(torch.equal(outs[first], o)) for name, o in outs.items()}
         same_graph = ("beam_shared" in outs and "beam_shared_graph" in outs
                       and bool(torch.equal(outs["beam_shared"], outs["beam_shared_graph"])))
         for rnd in range(a.rounds):
             secs = {}
             for name, kw in kinds:
-                s, out, cache = run(kw)
+                s, out, cache = run(kw, variant_of(name))
                 secs[name] = s
-                line = {"cache": name.split("+")[0], "loop": "smt" if name.endswith("+smt") else "transformers",
+                line = {"cache": name.split("+")[0].split("@")[0], "loop": "smt" if name.endswith("+smt") else "transformers",
                         "repetition_penalty": a.repetition_penalty,
                         "round": rnd, "model": a.model, "prompts": a.prompts, "beams": a.beams,
                         "prompt_len": a.prompt_len, "new_tokens": new, "seconds": round(s, 4),
                         "ms_per_token": round(1e3 * s / new, 3), "shape": list(out.shape),
                         f"same_tokens_as_{first}": same[name]}
+                if a.decode_linears is not None:
+                    line.update(decode_linears=variant_of(name), routed_launches=fused_llama.decode_linear_stats.as_dict())
+                    base = name.replace("@" + str(variant_of(name)), "")
+                    if variant_of(name) is not None and base in outs:
+                        line.update(same_tokens_as_unrouted=bool(torch.equal(outs[base], outs[name])))
                 if name.endswith("+smt"):
                     line.update(delegated=beam_search.stats.delegated)
                     if name.split("+")[0] in outs:
@@ -127,6 +170,11 @@ def main():
                 for other in ("beam_shared", "dynamic"):
                     if other in secs:
                         ratio[f"seconds_{other}_over_graph"] = round(secs[other] / secs["beam_shared_graph"], 3)
+            for v in a.decode_linears or ():
+                for lp in a.loop:
+                    base, dl = leg("beam_shared_graph", lp), leg(f"beam_shared_graph@{v}", lp)
+                    if base in secs and dl in secs:
+                        ratio[f"seconds_graph_over_{v}" + ("" if lp == "transformers" else "_" + lp)] = round(secs[base] / secs[dl], 3)
             for c in a.caches:
                 if c in secs and c + "+smt" in secs:
                     ratio[f"seconds_{c}_transformers_over_smt"] = round(secs[c] / secs[c + "+smt"], 3)

@@ -27,7 +27,8 @@ _DT = {torch.bfloat16: DTYPE_BF16, torch.float32: DTYPE_FP32, torch.float16: DTY
 ABI_VERSION = 13            # include/smt_hip.h: 16-bit dtype of the model ops / attention (v13),
                             # smt_adamw_args.param_dtype (v12), smt_wgrad_module.operand_dtype (v11)
 
-# Every function the headers declare (include/smt_hip.h, smt_model_ops.h, smt_attention.h, smt_fp8.h, smt_beam.h); tests check the
+# Every function the headers declare (include/smt_hip.h, smt_model_ops.h, smt_attention.h, smt_fp8.h, smt_beam.h,
+# smt_linear.h); tests check the
 # library exports each of them.
 ABI_FUNCTIONS = (
     "smt_last_error", "smt_abi_version", "smt_wgrad_workspace_bytes", "smt_tile_wgrad", "smt_wgrad_batch_workspace_bytes",
@@ -53,6 +54,7 @@ ABI_FUNCTIONS = (
     "smt_rmsnorm_fwd_quant_e4m3",
     "smt_rmsnorm_bwd_add_quant_e4m3",
     "smt_beam_last_error", "smt_beam_topk_workspace", "smt_beam_topk",
+    "smt_linear_last_error", "smt_linear_skinny_workspace", "smt_linear_skinny",
 )
 
 
@@ -122,6 +124,15 @@ class AttnShape(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("Hq", ctypes.c_int32), ("Hkv", ctypes.c_int32), ("S", ctypes.c_int32),
                 ("scale", ctypes.c_float), ("dtype", ctypes.c_int32)]       # ABI v13: SMT_DTYPE_BF16 / _FP16
 
+
+class SkinnyOut(ctypes.Structure):
+    """SmtSkinnyOut (include/smt_linear.h): one output of a decode-linear launch."""
+    _fields_ = [("w", ctypes.c_void_p), ("ldw", ctypes.c_int64), ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64),
+                ("N", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+SKINNY_PLAIN, SKINNY_SWIGLU = 0, 1
+SKINNY_MAX_M, SKINNY_MAX_OUT, SKINNY_KSPLIT = 16, 3, 8      # SMT_LINEAR_MAX_M / _MAX_OUT / _KSPLIT
 
 ACC_CHUNK = 4096
 _lock = threading.Lock()
@@ -226,6 +237,9 @@ _SIGS = {
     "smt_beam_topk_workspace": (_I64, [_I32, _I32, _I64, _I32]),
     "smt_beam_topk": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I64, _P, _P, _I64, _I32, ctypes.c_float, _P, _I32, _I32,
                                      _P, _P, _P, _P]),
+    "smt_linear_last_error": (ctypes.c_char_p, []),
+    "smt_linear_skinny_workspace": (_I64, [_I32, _I32, ctypes.POINTER(SkinnyOut), _I32, _I32]),
+    "smt_linear_skinny": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(SkinnyOut), _I32, _I32, _P, _P]),
 }
 
 
@@ -282,6 +296,8 @@ def _check(rc: int, what: str) -> None:
             err = lib.smt_attn_last_error
         elif what.startswith("smt_beam"):
             err = lib.smt_beam_last_error              # beam_kernels.hip
+        elif what.startswith("smt_linear"):
+            err = lib.smt_linear_last_error            # linear_kernels.hip
         else:
             err = lib.smt_last_error
         raise RuntimeError(f"{what} failed (status {rc}): {err().decode(errors='replace')}")
@@ -881,3 +897,33 @@ def channel_scores(acc: torch.Tensor, strategy: int) -> torch.Tensor:
                                   ws_bytes, _ptr(out), _stream(dev))
     _check(rc, "smt_channel_score")
     return out
+
+
+def linear_skinny(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: int = SKINNY_PLAIN,
+                  outs: Optional[Sequence[torch.Tensor]] = None) -> list:
+    """``[x @ W_i^T for W_i in weights]`` for at most 16 rows of ``x [M, K]`` (smt_linear_skinny,
+    include/smt_linear.h): one launch streams the 1..3 row-major ``[N_i, K]`` weights as they lie.
+    ``SKINNY_SWIGLU``: two weights of equal N, one result ``swiglu(x @ W_0^T, x @ W_1^T)``.
+    ``outs``: the result buffers (``[M, N_i]``, unit inner stride), allocated if not given."""
+    dev = _require_device(x, *weights)
+    dt = dtype_code16(x.dtype, "linear_skinny")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise RuntimeError(f"linear_skinny: x must be [M, K] with unit inner stride, got {tuple(x.shape)} / {x.stride()}")
+    M, K = x.shape
+    n_y = 1 if epilogue == SKINNY_SWIGLU else len(weights)
+    if outs is None:
+        outs = [torch.empty(M, w.shape[0], dtype=x.dtype, device=dev) for w in weights[:n_y]]
+    descs = (SkinnyOut * max(1, len(weights)))()
+    for i, w in enumerate(weights):
+        if w.dim() != 2 or w.shape[1] != K or w.stride(1) != 1 or w.dtype != x.dtype:
+            raise RuntimeError(f"linear_skinny: weight {i} must be [N, {K}] {x.dtype} with unit inner stride, got "
+                               f"{tuple(w.shape)} {w.dtype} / {w.stride()}")
+        descs[i].w, descs[i].ldw, descs[i].N = w.data_ptr(), w.stride(0), w.shape[0]
+        if i < n_y:
+            y = outs[i]
+            if tuple(y.shape) != (M, w.shape[0]) or y.stride(1) != 1 or y.dtype != x.dtype or y.device != dev:
+                raise RuntimeError(f"linear_skinny: output {i} must be [{M}, {w.shape[0]}] {x.dtype} on {dev}")
+            descs[i].y, descs[i].ldy = y.data_ptr(), y.stride(0)
+    _check(load().smt_linear_skinny(x.data_ptr(), x.stride(0), M, K, dt, descs, len(weights), int(epilogue), None,
+                                    _stream(dev)), "smt_linear_skinny")
+    return list(outs)

@@ -1,0 +1,265 @@
+// linear_kernels.hip — the decode linears on gfx950 (C ABI: include/smt_linear.h).
+//
+// y[M, N] = x[M, K] * W[N, K]^T for M <= 16: one read of W and almost no arithmetic, so the kernel is a
+// weight stream. One workgroup of WAVES waves owns 16 output features (one MFMA tile) of one output:
+//   - wave w takes the contiguous K-slice [w * c, (w + 1) * c) of the K / 32 steps, c = ceil(steps / WAVES);
+//   - a step is one v_mfma_f32_16x16x32 with W as the A operand (lane l: W[n0 + (l & 15)][k0 + 8 (l >> 4) + j],
+//     one non-temporal 16-byte load, no LDS staging) and x as the B operand (lane l: x[l & 15][same k], a
+//     default-policy 16-byte load that the L2 serves; lanes of rows >= M read row 0 and their column is dropped);
+//   - two batches of U steps' loads are in flight: the next batch is issued before the current one's MFMAs;
+//     a slice's last, partial batch is loaded whole too (clamped to the slice) and its spare MFMAs are skipped;
+//   - the waves' fp32 partials go through the LDS and wave 0 adds them in wave order, rounds once and
+//     stores: lane l holds features n0 + 4 (l >> 4) + 0..3 of x row l & 15, 8 contiguous bytes of y.
+// The x row is a column of the MFMA and columns never mix, so a row's result is a function of that row
+// and of W alone. Nothing here can wait for another workgroup.
+// SWIGLU: the workgroup streams the same 16 features of the gate and the up weight into two accumulators
+// and applies the SwiGLU forward of llama_kernels.hip to the two rounded products.
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "smt_hip.h"
+#include "smt_linear.h"
+#include "silu_math.h"
+
+namespace {
+
+thread_local char g_err[512] = "";
+
+int fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+constexpr int WAVES = SMT_LINEAR_KSPLIT;
+constexpr int THREADS = WAVES * 64;
+
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+
+// the 16-bit formats as llama_kernels.hip handles them (the SWIGLU epilogue must give its bits)
+template <int F> __device__ __forceinline__ float u2f(uint32_t b16) {
+    if constexpr (F == SMT_DTYPE_FP16) return (float)__builtin_bit_cast(_Float16, (uint16_t)b16);
+    else return __uint_as_float(b16 << 16);
+}
+template <int F> __device__ __forceinline__ uint32_t f2u(float f) {
+    if constexpr (F == SMT_DTYPE_FP16) {
+        asm("" : "+v"(f));
+        return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+    } else return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
+}
+template <int F> __device__ __forceinline__ float rnd(float f) {
+    uint32_t b = f2u<F>(f);
+    if constexpr (F == SMT_DTYPE_FP16) asm("" : "+v"(b));
+    return u2f<F>(b);
+}
+
+template <int F> __device__ __forceinline__ f32x4 mfma(const u32x4 a, const u32x4 b, const f32x4 c) {
+    if constexpr (F == SMT_DTYPE_FP16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+struct Params {
+    const uint16_t* x;
+    int64_t ldx;
+    const uint16_t* w[SMT_LINEAR_MAX_OUT];
+    int64_t ldw[SMT_LINEAR_MAX_OUT];
+    uint16_t* y[SMT_LINEAR_MAX_OUT];
+    int64_t ldy[SMT_LINEAR_MAX_OUT];
+    int32_t tile_end[SMT_LINEAR_MAX_OUT];      // PLAIN: running count of 16-feature tiles over the outputs
+    int32_t M, K;
+};
+
+// Steps [s, s + U) of a slice that ends at s_end, a step past the end replaced by the slice's last one (its
+// loads stay inside the slice and its MFMA is skipped; wave-uniform, so the clamp is scalar arithmetic): U
+// non-temporal 16-byte loads of each weight stream, U default-policy loads of x.
+template <int NW, int U>
+__device__ __forceinline__ void load_batch(u32x4 (&a)[NW][U], u32x4 (&b)[U], const uint16_t* const (&wp)[NW],
+                                           const uint16_t* xp, int s, int s_end) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t off = (int64_t)min(s + u, s_end - 1) * 32;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) a[i][u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wp[i] + off));
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) b[u] = *reinterpret_cast<const u32x4*>(xp + (int64_t)min(s + u, s_end - 1) * 32);
+}
+
+// NW weight streams (1: PLAIN, 2: SWIGLU's gate and up) against one x stream, U steps per batch.
+template <int F, int NW, int U>
+__global__ __launch_bounds__(THREADS)
+void skinny_kernel(const Params p) {
+    __shared__ f32x4 part[NW][WAVES][64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 15, h = lane >> 4;
+
+    int out = 0, tile = blockIdx.x;
+    if constexpr (NW == 1) {
+        out = (tile >= p.tile_end[0]) + (tile >= p.tile_end[1]);      // tile_end[i] is the total for i >= n_out
+        if (out) tile -= p.tile_end[out - 1];
+    }
+    const int n0 = tile * 16;
+    const uint16_t* wp[NW];
+    if constexpr (NW == 1) wp[0] = p.w[out] + (int64_t)(n0 + r) * p.ldw[out] + 8 * h;
+    else {
+        wp[0] = p.w[0] + (int64_t)(n0 + r) * p.ldw[0] + 8 * h;
+        wp[1] = p.w[1] + (int64_t)(n0 + r) * p.ldw[1] + 8 * h;
+    }
+    // lanes of rows >= M read row 0 instead (rows >= M are never touched); their column of the MFMA is
+    // computed and dropped, and no column reaches another
+    const bool row_live = r < p.M;
+    const uint16_t* xp = p.x + (int64_t)(row_live ? r : 0) * p.ldx + 8 * h;
+
+    const int steps = p.K >> 5;
+    const int per = (steps + WAVES - 1) / WAVES;
+    int s = wave * per;
+    const int s_end = min(steps, s + per);
+
+    f32x4 acc[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // batches of U steps, two in flight: the next batch's loads are issued before the current one's MFMAs
+    // wait for theirs. Only the last batch can be partial; no condition stands around a load (a branch there
+    // costs a vmcnt(0) each), the steps past the end are dropped at their MFMA.
+    const int n = s_end - s;
+    const int nb = (n + U - 1) / U;
+    if (nb > 0) {
+        u32x4 a[NW][U], b[U];
+        load_batch<NW, U>(a, b, wp, xp, s, s_end);
+        for (int i = 1; i < nb; ++i) {
+            u32x4 an[NW][U], bn[U];
+            load_batch<NW, U>(an, bn, wp, xp, s + i * U, s_end);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j) { acc[j] = mfma<F>(a[j][u], b[u], acc[j]); a[j][u] = an[j][u]; }
+                b[u] = bn[u];
+            }
+        }
+        const int left = n - (nb - 1) * U;                  // 1..U steps of the last batch are real
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (u < left) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j) acc[j] = mfma<F>(a[j][u], b[u], acc[j]);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int i = 0; i < NW; ++i) part[i][wave][lane] = acc[i];
+    __syncthreads();
+    if (wave != 0 || !row_live) return;
+
+    f32x4 sum[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        sum[i] = part[i][0][lane];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) sum[i] += part[i][w][lane];
+    }
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if constexpr (NW == 1) o[j] = f2u<F>(sum[0][j]);
+        else {
+            const float g = rnd<F>(sum[0][j]), up = rnd<F>(sum[1][j]);
+            const float sg = rnd<F>(g * smt_sigmoid(g));
+            o[j] = f2u<F>(sg * up);
+        }
+    }
+    uint16_t* yp = (NW == 1 ? p.y[out] + (int64_t)r * p.ldy[out] : p.y[0] + (int64_t)r * p.ldy[0]) + n0 + 4 * h;
+    *reinterpret_cast<uint2*>(yp) = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+}
+
+const char* check_sizes(int32_t M, int32_t K, const SmtSkinnyOut* outs, int32_t n_out, int32_t epilogue) {
+    if (M < 1 || M > SMT_LINEAR_MAX_M) return "M must lie in [1, 16]";
+    if (K < 32 || (K & 31)) return "K must be a positive multiple of 32";
+    if (epilogue != SMT_SKINNY_PLAIN && epilogue != SMT_SKINNY_SWIGLU) return "unknown epilogue";
+    if (n_out < 1 || n_out > SMT_LINEAR_MAX_OUT) return "n_out must lie in [1, 3]";
+    if (!outs) return "null outs";
+    int64_t tiles = 0;
+    for (int i = 0; i < n_out; ++i) {
+        if (outs[i].N < 16 || (outs[i].N & 15)) return "N must be a positive multiple of 16";
+        tiles += outs[i].N / 16;
+    }
+    if (tiles > 0x7fffffffLL) return "too many output features (grid size)";
+    if (epilogue == SMT_SKINNY_SWIGLU && (n_out != 2 || outs[0].N != outs[1].N)) return "SWIGLU takes two outputs of equal N";
+    return nullptr;
+}
+
+template <int F>
+int launch(const Params& p, int32_t epilogue, uint32_t grid, hipStream_t stream) {
+    if (epilogue == SMT_SKINNY_SWIGLU)
+        hipLaunchKernelGGL((skinny_kernel<F, 2, 4>), dim3(grid), dim3(THREADS), 0, stream, p);
+    else
+        hipLaunchKernelGGL((skinny_kernel<F, 1, 8>), dim3(grid), dim3(THREADS), 0, stream, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(-4, "smt_linear_skinny: %s", hipGetErrorString(e));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* smt_linear_last_error(void) { return g_err; }
+
+int64_t smt_linear_skinny_workspace(int32_t M, int32_t K, const SmtSkinnyOut* outs, int32_t n_out, int32_t epilogue) {
+    if (const char* why = check_sizes(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny_workspace: %s", why);
+    return 0;
+}
+
+int smt_linear_skinny(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t dtype, const SmtSkinnyOut* outs,
+                      int32_t n_out, int32_t epilogue, void* workspace, hipStream_t stream) {
+    (void)workspace;
+    if (const char* why = check_sizes(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny: %s", why);
+    if (dtype != SMT_DTYPE_BF16 && dtype != SMT_DTYPE_FP16)
+        return fail(-1, "smt_linear_skinny: dtype %d is not SMT_DTYPE_BF16 / _FP16", (int)dtype);
+    const int n_y = epilogue == SMT_SKINNY_SWIGLU ? 1 : n_out;
+    if (!x) return fail(-1, "smt_linear_skinny: null x");
+    if (ldx < K) return fail(-1, "smt_linear_skinny: ldx %lld < K %d", (long long)ldx, (int)K);
+    for (int i = 0; i < n_out; ++i) {
+        if (!outs[i].w || (i < n_y && !outs[i].y)) return fail(-1, "smt_linear_skinny: null w or y of output %d", i);
+        if (outs[i].ldw < K || (i < n_y && outs[i].ldy < outs[i].N))
+            return fail(-1, "smt_linear_skinny: ldw or ldy of output %d below its extent", i);
+    }
+    if (!aligned16(x) || (ldx & 7)) return fail(-2, "smt_linear_skinny: x must be 16-byte aligned, ldx %lld a multiple of 8", (long long)ldx);
+    for (int i = 0; i < n_out; ++i) {
+        if (!aligned16(outs[i].w) || (outs[i].ldw & 7) || (i < n_y && (!aligned16(outs[i].y) || (outs[i].ldy & 7))))
+            return fail(-2, "smt_linear_skinny: w, y of output %d must be 16-byte aligned, ldw, ldy multiples of 8", i);
+    }
+    Params p = {};
+    p.x = static_cast<const uint16_t*>(x);
+    p.ldx = ldx;
+    p.M = M;
+    p.K = K;
+    int32_t tiles = 0;
+    for (int i = 0; i < SMT_LINEAR_MAX_OUT; ++i) {
+        if (i < n_out) {
+            p.w[i] = static_cast<const uint16_t*>(outs[i].w);
+            p.ldw[i] = outs[i].ldw;
+            p.y[i] = static_cast<uint16_t*>(outs[i].y);
+            p.ldy[i] = outs[i].ldy;
+            tiles += outs[i].N / 16;
+        }
+        p.tile_end[i] = tiles;
+    }
+    const uint32_t grid = (uint32_t)(epilogue == SMT_SKINNY_SWIGLU ? outs[0].N / 16 : tiles);
+    if (dtype == SMT_DTYPE_BF16) return launch<SMT_DTYPE_BF16>(p, epilogue, grid, stream);
+    return launch<SMT_DTYPE_FP16>(p, epilogue, grid, stream);
+}
+
+}  // extern "C"

@@ -19,6 +19,11 @@ The causal-LM loss (transformers ``ForCausalLMLoss``: ``logits.float()`` then cr
 two row kernels over the bf16 logits (``smt_ce_fwd`` / ``smt_ce_bwd``), so the 16.8 GB fp32 logits
 copy, its log-softmax and its fp32 gradient are never materialised (tests/test_gpu_cross_entropy.py).
 
+``patch_llama(decode_linears=True)`` (opt-in) routes the dense linears of a decode step (at most 16 rows,
+gradients off) to a weight-streaming kernel (``csrc/linear_kernels.hip``, C ABI ``include/smt_linear.h``;
+:func:`decode_linear`, :func:`decode_linear_group`, :func:`decode_swiglu`) at the sizes where it measured
+faster than hipBLASLt (tests/test_gpu_decode_linear.py, tests/test_gpu_generate_decode_linears.py).
+
 The model's dtype is bf16 or, since ABI v13, fp16 (the reference's ``--dtype fp16``,
 ``fine_tune.py:955-959``): every kernel is one template body for both formats, rounding where the eager
 chain rounds to the model's dtype (tests/test_gpu_fused_fp16.py). fp32 models and mixed dtypes raise
@@ -468,9 +473,246 @@ def _grad_or_placeholder(like: torch.Tensor, grad, need) -> torch.Tensor:
     return ph
 
 
+# ------------------------------------------------------------------------------------------------
+# decode linears (opt-in: patch_llama(decode_linears=True))
+# ------------------------------------------------------------------------------------------------
+class DecodeLinearStats:
+    """Routed launches of the decode-linear kernel by kind (``single``, ``group``: q/k/v in one launch,
+    ``swiglu``: gate, up and SwiGLU in one launch). A graph replay runs no Python and counts nothing."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.single = 0
+        self.group = 0
+        self.swiglu = 0
+
+    def as_dict(self) -> dict:
+        return {"single": self.single, "group": self.group, "swiglu": self.swiglu}
+
+
+decode_linear_stats = DecodeLinearStats()
+# the two fused launches of the routing, read at call time (scripts/generate_cache_bench.py times the token with
+# each off): q/k/v as one grouped launch, and gate/up/SwiGLU as one launch
+DECODE_LINEAR_GROUP = True
+DECODE_LINEAR_SWIGLU = True
+# The routing's size rule: a launch goes to the kernel only if K <= 4096 and its weights hold at most 2^25
+# elements (sum of N times K; 64 MiB of 16-bit weights). Every measured launch inside the rule, (N, K) =
+# (4096, 4096), (1024, 4096) and the grouped (6144, 4096), is 1.3-3.0x faster than hipBLASLt, which sits on a
+# floor of about 15 us per launch there; every measured launch outside it (K = 5120 and up, or N = 13824 and
+# up) is slower or inside the baseline's own spread, 0.47-1.01x: hipBLASLt streams those at 0.40-0.74 of 8 TB/s
+# (profiles/r20_decode_linear_bench.jsonl, DESIGN 4c).
+DECODE_LINEAR_MAX_K = 4096
+DECODE_LINEAR_MAX_WEIGHT_ELEMS = 1 << 25
+
+
+def _decode_routes(x, weights, biases=(), need_cuda: bool = True) -> bool:
+    """The routing's decision for one launch: :func:`decode_linear_reason` admits it and the size rule holds."""
+    return (decode_linear_reason(x, weights, biases, need_cuda) is None
+            and x.shape[-1] <= DECODE_LINEAR_MAX_K
+            and sum(w.shape[0] for w in weights) * x.shape[-1] <= DECODE_LINEAR_MAX_WEIGHT_ELEMS)
+
+
+def _aligned16(t: torch.Tensor) -> bool:
+    return (t.storage_offset() * t.element_size()) % 16 == 0 and (t.device.type == "meta" or t.data_ptr() % 16 == 0)
+
+
+def decode_linear_reason(x: torch.Tensor, weights, biases=(), need_cuda: bool = True):
+    """Why ``x @ W^T`` for these weights cannot go to the decode-linear kernel (smt_linear_skinny), or
+    None if it can. The one predicate of the routing; every condition of include/smt_linear.h:
+    gradients off; ROCm bf16 / fp16 tensors of one dtype; 1..16 rows after flattening the leading
+    dimensions; no bias and no fp8 copy on a weight; K % 32 == 0, N % 16 == 0; unit inner strides, row
+    strides multiples of 8 and 16-byte aligned storage. ``need_cuda=False`` lifts the device condition
+    (the host tests run the rest on CPU and meta tensors)."""
+    if torch.is_grad_enabled():
+        return "gradients are enabled"
+    if any(b is not None for b in biases):
+        return "bias"
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        return f"dtype {x.dtype}"
+    if need_cuda and x.device.type != "cuda":
+        return f"device {x.device}"
+    if x.dim() < 1 or x.shape[-1] == 0:
+        return "x has no feature dimension"
+    K = x.shape[-1]
+    rows = x.numel() // K
+    if not 1 <= rows <= _hip.SKINNY_MAX_M:
+        return f"{rows} rows"
+    if K % 32:
+        return f"K {K} is not a multiple of 32"
+    if x.stride(-1) != 1 or not _aligned16(x):
+        return "x inner stride or alignment"
+    if not (x.is_contiguous() or (x.dim() == 2 and x.stride(0) % 8 == 0 and x.stride(0) >= K)):
+        return "x rows do not flatten to one aligned stride"
+    if not 1 <= len(weights) <= _hip.SKINNY_MAX_OUT:
+        return f"{len(weights)} weights"
+    for w in weights:
+        if w.dim() != 2 or w.shape[1] != K:
+            return f"weight shape {tuple(w.shape)} for K {K}"
+        if w.dtype != x.dtype or w.device != x.device:
+            return f"weight {w.dtype} on {w.device} beside x {x.dtype} on {x.device}"
+        if getattr(w, "_smt_fp8", None) is not None:
+            return "fp8 weight"
+        if w.shape[0] == 0 or w.shape[0] % 16:
+            return f"N {w.shape[0]} is not a multiple of 16"
+        if w.stride(1) != 1 or w.stride(0) % 8 or w.stride(0) < K or not _aligned16(w):
+            return "weight stride or alignment"
+    return None
+
+
+def _decode_call(x, weights, epilogue, what):
+    why = decode_linear_reason(x, weights)
+    if why is not None:                 # no quiet fall-back: the routing asks the predicate first
+        raise RuntimeError(f"{what}: the call does not qualify for the decode-linear kernel ({why})")
+    if epilogue == _hip.SKINNY_SWIGLU and weights[0].shape[0] != weights[1].shape[0]:
+        raise RuntimeError(f"{what}: gate and up of unequal width")
+    K = x.shape[-1]
+    ys = _hip.linear_skinny(x.reshape(-1, K), list(weights), epilogue)
+    return [y.view(*x.shape[:-1], y.shape[-1]) for y in ys]
+
+
+def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """``x @ weight^T`` for at most 16 rows of ``x``: the weight-streaming kernel on a ROCm device (an
+    error if the call does not qualify, :func:`decode_linear_reason`), torch's matmul on the CPU."""
+    if x.device.type != "cuda":
+        return torch.matmul(x, weight.t())
+    y = _decode_call(x, (weight,), _hip.SKINNY_PLAIN, "decode_linear")[0]
+    decode_linear_stats.single += 1
+    return y
+
+
+def decode_linear_group(x: torch.Tensor, weights) -> list:
+    """``[x @ W^T for W in weights]`` (1..3 weights) as one launch that reads ``x`` once; bit for bit
+    the single calls."""
+    if x.device.type != "cuda":
+        return [torch.matmul(x, w.t()) for w in weights]
+    ys = _decode_call(x, tuple(weights), _hip.SKINNY_PLAIN, "decode_linear_group")
+    decode_linear_stats.group += 1
+    return ys
+
+
+def decode_swiglu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor) -> torch.Tensor:
+    """``silu(x @ w_gate^T) * (x @ w_up^T)`` as one launch; bit for bit two :func:`decode_linear` calls
+    and the fused SwiGLU forward. On the CPU, torch's chain."""
+    if x.device.type != "cuda":
+        return torch.nn.functional.silu(torch.matmul(x, w_gate.t())) * torch.matmul(x, w_up.t())
+    y = _decode_call(x, (w_gate, w_up), _hip.SKINNY_SWIGLU, "decode_swiglu")[0]
+    decode_linear_stats.swiglu += 1
+    return y
+
+
+def _sync_for_decode(*mods) -> None:
+    """The SMT modules' write-back of their tiles into W, as their own forward does first."""
+    for m in mods:
+        if getattr(m, "writeback_on_forward", False) and hasattr(m, "sync_weight"):
+            m.sync_weight()
+
+
+def _decode_prev_forward(self, x):
+    prev = self.__dict__.get("_smt_decode_prev_forward")
+    return prev(x) if prev is not None else type(self).forward(self, x)
+
+
+def decode_routed_linear_forward(self, x):
+    """Instance forward of a routed projection: a qualifying call (a decode step) goes to the kernel,
+    anything else to the forward the module had. A q_proj with ``_smt_decode_group`` computes k_proj's and
+    v_proj's outputs in the same launch and attaches them to ``x``; k_proj and v_proj take them only from
+    that very tensor at the same version and for their own weight."""
+    st = x.__dict__.get("_smt_decode_kv") if isinstance(x, torch.Tensor) else None
+    if st is not None:
+        if st[0] == x._version and not torch.is_grad_enabled():
+            for i in (1, 3):
+                if st[i] is self.weight and st[i + 1] is not None:
+                    y = st[i + 1]
+                    st[i + 1] = None
+                    if st[2] is None and st[4] is None:
+                        del x.__dict__["_smt_decode_kv"]
+                    return y
+        else:
+            del x.__dict__["_smt_decode_kv"]
+    bias = getattr(self, "bias", None)
+    group = self.__dict__.get("_smt_decode_group")
+    if group is not None and DECODE_LINEAR_GROUP:
+        kv = [r() for r in group]
+        if all(m is not None for m in kv):
+            ws = (self.weight, kv[0].weight, kv[1].weight)
+            if _decode_routes(x, ws, (bias, kv[0].bias, kv[1].bias)):
+                _sync_for_decode(self, *kv)
+                q, k, v = decode_linear_group(x, ws)
+                x.__dict__["_smt_decode_kv"] = [x._version, ws[1], k, ws[2], v]
+                return q
+    if _decode_routes(x, (self.weight,), (bias,)):
+        _sync_for_decode(self)
+        return decode_linear(x, self.weight)
+    return _decode_prev_forward(self, x)
+
+
+def _decode_routable(m) -> bool:
+    from .smt.smt import LinearLayer_MatrixSparsity
+    return (type(m) is nn.Linear or isinstance(m, LinearLayer_MatrixSparsity)) and "_smt_decode_routed" not in m.__dict__
+
+
+def _route_decode_linear(m) -> None:
+    if "forward" in m.__dict__:
+        m.__dict__["_smt_decode_prev_forward"] = m.__dict__["forward"]
+    m.forward = decode_routed_linear_forward.__get__(m, type(m))
+    m.__dict__["_smt_decode_routed"] = True
+
+
+def _unroute_decode_linear(m) -> None:
+    if m.__dict__.pop("_smt_decode_routed", None):
+        m.__dict__.pop("forward", None)
+        prev = m.__dict__.pop("_smt_decode_prev_forward", None)
+        if prev is not None:
+            m.__dict__["forward"] = prev
+    m.__dict__.pop("_smt_decode_group", None)
+
+
+def route_decode_linears(model: nn.Module) -> int:
+    """What ``patch_llama(decode_linears=True)`` adds, by itself: the routed forwards of the projections
+    and of a bias-free ``lm_head``, the q/k/v group and the MLPs' fused launch. Returns the number of linears
+    routed by this call. :func:`unroute_decode_linears` (and :func:`unpatch_llama`) removes all of it."""
+    ml = _ml()
+    routed = 0
+    for m in model.modules():
+        if isinstance(m, ml.LlamaAttention):
+            names = ("q_proj", "k_proj", "v_proj", "o_proj")
+        elif isinstance(m, ml.LlamaMLP):
+            names = ("gate_proj", "up_proj", "down_proj")
+            m.__dict__["_smt_decode_linears"] = True
+        elif isinstance(m, ml.LlamaForCausalLM):
+            names = ("lm_head",) if getattr(getattr(m, "lm_head", None), "bias", None) is None else ()
+        else:
+            continue
+        for n in names:
+            lin = getattr(m, n, None)
+            if lin is not None and _decode_routable(lin):
+                _route_decode_linear(lin)
+                routed += 1
+        if isinstance(m, ml.LlamaAttention) and all(
+                getattr(m, n, None) is not None and getattr(m, n).__dict__.get("_smt_decode_routed") for n in names[:3]):
+            m.q_proj.__dict__["_smt_decode_group"] = (weakref.ref(m.k_proj), weakref.ref(m.v_proj))
+    return routed
+
+
+def unroute_decode_linears(model: nn.Module) -> None:
+    for m in model.modules():
+        m.__dict__.pop("_smt_decode_linears", None)
+        _unroute_decode_linear(m)
+
+
 def fused_mlp_forward(self, x):
     """Drop-in for ``LlamaMLP.forward`` (SiLU activation). With an fp8 down_proj the SwiGLU also emits
     down_proj's quantised input; a frozen plain down_proj then never reads the bf16 activation."""
+    if self.__dict__.get("_smt_decode_linears") and DECODE_LINEAR_SWIGLU:
+        # patch_llama(decode_linears=True): gate, up and the SwiGLU of a decode step as one launch
+        g, u = self.gate_proj, self.up_proj
+        if (g.__dict__.get("_smt_decode_routed") and u.__dict__.get("_smt_decode_routed")
+                and g.weight.shape[0] == u.weight.shape[0]
+                and _decode_routes(x, (g.weight, u.weight), (g.bias, u.bias))):
+            _sync_for_decode(g, u)
+            return self.down_proj(decode_swiglu(x, g.weight, u.weight))
     from .fp8 import sole_swiglu_consumer
     with sole_swiglu_consumer():             # gate / up feed only the SwiGLU below
         gate, up = self.gate_proj(x), self.up_proj(x)
@@ -1624,7 +1866,8 @@ def _keep_2d_mask(config=None, inputs_embeds=None, attention_mask=None, **kwargs
     return attention_mask
 
 
-def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_head_loss: bool = None) -> dict:
+def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_head_loss: bool = None,
+                decode_linears: bool = False) -> dict:
     """Route a transformers LLaMA model's RMSNorm / RoPE / SwiGLU / attention-residual add (and, with ``attention``, its
     attention; with ``loss``, its causal-LM loss) through the fused kernels. RoPE is patched at
     module level (``modeling_llama.apply_rotary_pos_emb``, looked up by ``LlamaAttention.forward`` at
@@ -1638,7 +1881,15 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
     With ``attention``, ``generation_config.disable_compile`` is set and the model keeps the 2-D mask
     in ``generate()`` (``create_masks_for_generate``), so that ``cache_implementation="static"`` runs
     the kernels eagerly; :func:`unpatch_llama` restores both.
-    Returns counts of patched modules. Idempotent."""
+    ``decode_linears`` (off by default; nothing below exists on a model patched without it): the q/k/v/o and
+    gate/up/down projections that are ``nn.Linear`` or ``LinearLayer_MatrixSparsity``, and a bias-free
+    ``lm_head``, get :func:`decode_routed_linear_forward`: calls that :func:`decode_linear_reason` admits (no
+    gradients, at most 16 rows: the decode steps) run the weight-streaming kernel of ``include/smt_linear.h``,
+    q/k/v as one launch and gate/up/SwiGLU as one launch, where K is within
+    ``DECODE_LINEAR_MAX_K`` and the launch's weights within ``DECODE_LINEAR_MAX_WEIGHT_ELEMS`` (the shapes at
+    which the kernel measured faster than hipBLASLt); every
+    other call runs what it ran before.
+    Returns counts of patched modules (with ``decode_linears``, also the routed linears). Idempotent."""
     ml = _ml()
     counts = {"rmsnorm": 0, "mlp": 0, "rope": 1, "attention": 0, "loss": 0, "decoder": 0, "lm_head_loss": 0}
     if lm_head_loss is None:
@@ -1692,6 +1943,8 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
             for i in range(len(m) - 1):
                 m[i].__dict__["_smt_next_layer"] = weakref.ref(m[i + 1])
     ml.apply_rotary_pos_emb = fused_apply_rotary_pos_emb
+    if decode_linears:
+        counts["decode_linears"] = route_decode_linears(model)
     return counts
 
 
@@ -1717,3 +1970,4 @@ def unpatch_llama(model: nn.Module = None) -> None:
             if isinstance(m, (ml.LlamaRMSNorm, ml.LlamaMLP, ml.LlamaDecoderLayer)) and "forward" in m.__dict__:
                 del m.__dict__["forward"]
             m.__dict__.pop("_smt_next_layer", None)
+        unroute_decode_linears(model)
