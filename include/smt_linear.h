@@ -66,6 +66,55 @@ int64_t smt_linear_skinny_workspace(int32_t M, int32_t K, const SmtSkinnyOut* ou
 int smt_linear_skinny(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t dtype, const SmtSkinnyOut* outs,
                       int32_t n_out, int32_t epilogue, void* workspace, hipStream_t stream);
 
+/*
+ * The same stream on e4m3 operands (the fp8 path's frozen linears): x8 [M][ldx] e4m3fn bytes with one fp32
+ * scale per row, sx [M]; each of the 1..3 outputs w8 [N][ldw] e4m3fn bytes with one fp32 scale per output
+ * feature, sw [N]: exactly what smt_quant_rows_e4m3 (smt_fp8.h) writes. y is bf16 or fp16 (`out_dtype`).
+ *
+ *     y[m][n] = RN_out( RN32( acc[m][n] * RN32(sx[m] * sw[n]) ) ),
+ *     acc[m][n] = sum_k dec(x8[m][k]) * dec(w8[n][k])  in fp32
+ *
+ * The order of the two scale multiplications is part of the contract: first the two scales, rounded to fp32,
+ * then the accumulator times that product, rounded to fp32, then one rounding to the output dtype.
+ *
+ * A step is 64 K-elements of a 16-feature tile: one non-temporal 16-byte load per lane of w8, one default-
+ * policy 16-byte load of x8, and two v_mfma_f32_16x16x32_fp8_fp8 (bytes 0..7 and 8..15 of the two loads; the
+ * instruction pairs slot j of a lane's A bytes with slot j of the same lane group's B bytes, so any
+ * assignment of bytes to K positions is right when both operands use the same one). The block-scaled
+ * 16x16x128 form would take 32 bytes per lane and operand and force K % 128; at these shapes the kernel waits
+ * for memory, not for the matrix core, so its higher rate buys nothing.
+ *
+ * Sizes and alignment: K % 64 == 0, N % 16 == 0; ldx, ldw multiples of 16 (bytes) with ldx >= K, ldw >= K;
+ * ldy a multiple of 8 elements, ldy >= N; x8, w8, sw and y 16-byte aligned (sx: 4-byte).
+ * Everything else is smt_linear_skinny's contract: SMT_LINEAR_KSPLIT contiguous K-slices (of the K / 64
+ * steps) added in wave order, no atomics, bit-reproducible; a row's output is a function of that row of x8,
+ * its sx and of the weights alone; rows >= M of x8 and sx are never read; nothing of y is written outside
+ * [0, M) x [0, N); no synchronisation between workgroups, so the workspace query returns 0; one launch, no
+ * allocation, launch parameters from shapes and pointers only; the same return codes.
+ *
+ * SMT_SKINNY_PLAIN: n_out 1..3, each output with its own sw; x8 is read once. SMT_SKINNY_SWIGLU: n_out == 2,
+ * equal N; the scaled gate and up are each rounded to the dtype first, then the SwiGLU forward of
+ * smt_model_ops.h: bit for bit the chain of two PLAIN calls and that kernel.
+ */
+typedef struct {
+    const void* w8;               /* [N][ldw] e4m3fn bytes */
+    const float* sw;              /* [N] */
+    int64_t ldw;
+    void* y;                      /* [M][ldy] of out_dtype */
+    int64_t ldy;
+    int32_t N;
+    int32_t reserved;
+} SmtSkinnyFp8Out;
+
+/* Bytes of workspace for smt_linear_skinny_fp8 with these sizes (0 today); -1 if they are invalid. */
+int64_t smt_linear_skinny_fp8_workspace(int32_t M, int32_t K, const SmtSkinnyFp8Out* outs, int32_t n_out,
+                                        int32_t epilogue);
+
+/* out_dtype: SMT_DTYPE_BF16 / SMT_DTYPE_FP16. outs: HOST array of n_out entries. */
+int smt_linear_skinny_fp8(const void* x8, int64_t ldx, const float* sx, int32_t M, int32_t K, int32_t out_dtype,
+                          const SmtSkinnyFp8Out* outs, int32_t n_out, int32_t epilogue, void* workspace,
+                          hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

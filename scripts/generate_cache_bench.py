@@ -29,7 +29,14 @@ neither, ``nogroup`` / ``noswiglu`` = without the one, ``unbounded*`` = the same
 rule, every qualifying launch on the kernel). The routing is put on and taken off between legs
 (``route_decode_linears`` / ``unroute_decode_linears``), outside the timing; the leg without the flag runs
 the modules as ``patch_llama(model)`` leaves them. The ratio line carries
-``seconds_graph_over_<variant>`` per loop."""
+``seconds_graph_over_<variant>`` per loop.
+
+``--fp8`` adds, for every ``beam_shared_graph`` leg, three legs on a second model of the same weights, frozen,
+with ``engine.attach_fp8_weights`` (config 5): ``fp8_base`` = that model as ``patch_llama(model)`` leaves it
+(``fp8.quant_rows`` + ``torch._scaled_mm`` per projection: the baseline of the other two), ``fp8`` = with
+``patch_llama(decode_linears=True, decode_fp8=True)``'s routing and its ``DECODE_FP8_*`` size rule, and
+``fp8_unbounded`` = the same with the rule removed (every qualifying launch on the e4m3 kernel). Their lines carry
+``fp8_launches`` (``decode_fp8_stats``) and the ratio line ``seconds_fp8_base_over_<variant>`` per loop."""
 import argparse
 import json
 import os
@@ -51,6 +58,7 @@ DL_VARIANTS = {"all": (True, True, DL_RULE), "single": (False, False, DL_RULE), 
                "noswiglu": (True, False, DL_RULE), "unbounded": (True, True, 1 << 62),
                "unbounded_single": (False, False, 1 << 62), "unbounded_nogroup": (False, True, 1 << 62),
                "unbounded_noswiglu": (True, False, 1 << 62)}
+FP8_VARIANTS = {"fp8_base": None, "fp8": True, "fp8_unbounded": False}      # variant: DECODE_FP8_RULE (None: unrouted)
 
 
 def main():
@@ -67,6 +75,8 @@ def main():
                     choices=["dynamic", "static", "beam_shared", "beam_shared_graph"])
     ap.add_argument("--decode-linears", nargs="*", default=None, choices=sorted(DL_VARIANTS),
                     help="add beam_shared_graph legs on a model patched with decode_linears=True")
+    ap.add_argument("--fp8", action="store_true",
+                    help="add beam_shared_graph legs on a frozen model with attach_fp8_weights: " + " ".join(FP8_VARIANTS))
     a = ap.parse_args()
     if a.decode_linears is not None and not a.decode_linears:
         a.decode_linears = ["all"]
@@ -76,6 +86,15 @@ def main():
     model = build_model(a.model, dev).eval()
     model.generation_config.pad_token_id = 0
     patch_llama(model)
+    fp8_model = None
+    if a.fp8:
+        from sparse_matrix_tuning_amd import engine
+        fp8_model = build_model(a.model, dev).eval()          # the same seed: the same weights
+        fp8_model.generation_config.pad_token_id = 0
+        for p in fp8_model.parameters():
+            p.requires_grad_(False)
+        engine.attach_fp8_weights(fp8_model)
+        patch_llama(fp8_model)
     g = torch.Generator().manual_seed(0)
     ids = torch.randint(3, MODELS[a.model]["vocab_size"], (a.prompts, a.prompt_len), generator=g)
     mask = torch.ones_like(ids)
@@ -105,7 +124,8 @@ def main():
         extra = {} if a.repetition_penalty == 1.0 else {"repetition_penalty": a.repetition_penalty}
         loops = {"transformers": {}, "smt": {"custom_generate": beam_search.smt_beam_search}}
         leg = lambda cache, loop: cache if loop == "transformers" else f"{cache}+{loop}"
-        variants = lambda c: [None] + (list(a.decode_linears or ()) if c == "beam_shared_graph" else [])
+        variants = lambda c: [None] + ((list(a.decode_linears or ()) + (list(FP8_VARIANTS) if a.fp8 else []))
+                                       if c == "beam_shared_graph" else [])
         kinds = tuple((leg(c if v is None else f"{c}@{v}", lp), (lambda c=c, lp=lp: {**caches[c](), **loops[lp], **extra}))
                       for c in a.caches for v in variants(c) for lp in a.loop)
         first = kinds[0][0]
@@ -116,7 +136,16 @@ def main():
             """The model patched for variant ``v`` (None: without the decode linears)."""
             if v != routed["now"]:
                 fused_llama.unroute_decode_linears(model)
-                if v is not None:
+                if fp8_model is not None:
+                    fused_llama.unroute_decode_linears(fp8_model)
+                if v in FP8_VARIANTS:
+                    if FP8_VARIANTS[v] is not None:
+                        fused_llama.route_decode_linears(fp8_model, fp8=True)
+                        fused_llama.DECODE_FP8_RULE = FP8_VARIANTS[v]
+                        (fused_llama.DECODE_LINEAR_GROUP, fused_llama.DECODE_LINEAR_SWIGLU,
+                         fused_llama.DECODE_LINEAR_MAX_WEIGHT_ELEMS) = DL_VARIANTS["all"]
+                        fused_llama.DECODE_LINEAR_MAX_K = DL_MAX_K
+                elif v is not None:
                     fused_llama.route_decode_linears(model)
                     (fused_llama.DECODE_LINEAR_GROUP, fused_llama.DECODE_LINEAR_SWIGLU,
                      fused_llama.DECODE_LINEAR_MAX_WEIGHT_ELEMS) = DL_VARIANTS[v]
@@ -127,11 +156,13 @@ def main():
             route(v)
             kw = kw()
             fused_llama.decode_linear_stats.reset()
+            fused_llama.decode_fp8_stats.reset()
             beam_search.stats.reset()
+            m = fp8_model if v in FP8_VARIANTS else model
             torch.cuda.synchronize()
             t = time.perf_counter()
             with torch.no_grad():
-                out = model.generate(input_ids=ids, attention_mask=mask, num_beams=a.beams, do_sample=False,
+                out = m.generate(input_ids=ids, attention_mask=mask, num_beams=a.beams, do_sample=False,
                                      max_new_tokens=new, min_new_tokens=new, **kw)
             torch.cuda.synchronize()
             return time.perf_counter() - t, out, kw.get("past_key_values")
@@ -151,9 +182,11 @@ def main():
                         "prompt_len": a.prompt_len, "new_tokens": new, "seconds": round(s, 4),
                         "ms_per_token": round(1e3 * s / new, 3), "shape": list(out.shape),
                         f"same_tokens_as_{first}": same[name]}
-                if a.decode_linears is not None:
+                if a.decode_linears is not None or a.fp8:
                     line.update(decode_linears=variant_of(name), routed_launches=fused_llama.decode_linear_stats.as_dict())
-                    base = name.replace("@" + str(variant_of(name)), "")
+                    if variant_of(name) in FP8_VARIANTS:
+                        line.update(fp8_launches=fused_llama.decode_fp8_stats.as_dict())
+                    base = name.replace("@" + str(variant_of(name)), "@fp8_base" if variant_of(name) in FP8_VARIANTS else "")
                     if variant_of(name) is not None and base in outs:
                         line.update(same_tokens_as_unrouted=bool(torch.equal(outs[base], outs[name])))
                 if name.endswith("+smt"):
@@ -175,6 +208,11 @@ def main():
                     base, dl = leg("beam_shared_graph", lp), leg(f"beam_shared_graph@{v}", lp)
                     if base in secs and dl in secs:
                         ratio[f"seconds_graph_over_{v}" + ("" if lp == "transformers" else "_" + lp)] = round(secs[base] / secs[dl], 3)
+            for v in (v for v in FP8_VARIANTS if a.fp8 and v != "fp8_base"):
+                for lp in a.loop:
+                    base, dl = leg("beam_shared_graph@fp8_base", lp), leg(f"beam_shared_graph@{v}", lp)
+                    if base in secs and dl in secs:
+                        ratio[f"seconds_fp8_base_over_{v}" + ("" if lp == "transformers" else "_" + lp)] = round(secs[base] / secs[dl], 3)
             for c in a.caches:
                 if c in secs and c + "+smt" in secs:
                     ratio[f"seconds_{c}_transformers_over_smt"] = round(secs[c] / secs[c + "+smt"], 3)

@@ -55,6 +55,7 @@ ABI_FUNCTIONS = (
     "smt_rmsnorm_bwd_add_quant_e4m3",
     "smt_beam_last_error", "smt_beam_topk_workspace", "smt_beam_topk",
     "smt_linear_last_error", "smt_linear_skinny_workspace", "smt_linear_skinny",
+    "smt_linear_skinny_fp8_workspace", "smt_linear_skinny_fp8",
 )
 
 
@@ -129,6 +130,12 @@ class SkinnyOut(ctypes.Structure):
     """SmtSkinnyOut (include/smt_linear.h): one output of a decode-linear launch."""
     _fields_ = [("w", ctypes.c_void_p), ("ldw", ctypes.c_int64), ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64),
                 ("N", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class SkinnyFp8Out(ctypes.Structure):
+    """SmtSkinnyFp8Out (include/smt_linear.h): one output of an e4m3 decode-linear launch."""
+    _fields_ = [("w8", ctypes.c_void_p), ("sw", ctypes.c_void_p), ("ldw", ctypes.c_int64), ("y", ctypes.c_void_p),
+                ("ldy", ctypes.c_int64), ("N", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 SKINNY_PLAIN, SKINNY_SWIGLU = 0, 1
@@ -240,6 +247,8 @@ _SIGS = {
     "smt_linear_last_error": (ctypes.c_char_p, []),
     "smt_linear_skinny_workspace": (_I64, [_I32, _I32, ctypes.POINTER(SkinnyOut), _I32, _I32]),
     "smt_linear_skinny": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(SkinnyOut), _I32, _I32, _P, _P]),
+    "smt_linear_skinny_fp8_workspace": (_I64, [_I32, _I32, ctypes.POINTER(SkinnyFp8Out), _I32, _I32]),
+    "smt_linear_skinny_fp8": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _I32, ctypes.POINTER(SkinnyFp8Out), _I32, _I32, _P, _P]),
 }
 
 
@@ -926,4 +935,42 @@ def linear_skinny(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: in
             descs[i].y, descs[i].ldy = y.data_ptr(), y.stride(0)
     _check(load().smt_linear_skinny(x.data_ptr(), x.stride(0), M, K, dt, descs, len(weights), int(epilogue), None,
                                     _stream(dev)), "smt_linear_skinny")
+    return list(outs)
+
+
+def _bytes2d(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dim() != 2 or t.element_size() != 1 or t.stride(1) != 1:
+        raise RuntimeError(f"linear_skinny_fp8: {what} must be 2-D e4m3 bytes with unit inner stride, got "
+                           f"{tuple(t.shape)} {t.dtype} / {t.stride()}")
+    return t
+
+
+def linear_skinny_fp8(x8: torch.Tensor, sx: torch.Tensor, weights: Sequence[tuple], out_dtype: torch.dtype,
+                      epilogue: int = SKINNY_PLAIN, outs: Optional[Sequence[torch.Tensor]] = None) -> list:
+    """:func:`linear_skinny` on e4m3 operands (smt_linear_skinny_fp8): ``x8 [M, K]`` bytes (uint8 or
+    float8_e4m3fn) with its row scales ``sx [M]`` fp32, and 1..3 ``weights`` as pairs ``(w8 [N_i, K], sw [N_i])``,
+    read where they lie. Results in ``out_dtype`` (bf16 / fp16), written into ``outs`` when given."""
+    dev = _require_device(x8, sx, *[t for pair in weights for t in pair])
+    dt = dtype_code16(out_dtype, "linear_skinny_fp8")
+    _bytes2d(x8, "x8")
+    M, K = x8.shape
+    if sx.dtype != torch.float32 or sx.numel() < M or not sx.is_contiguous():
+        raise RuntimeError(f"linear_skinny_fp8: sx must be contiguous fp32 with at least {M} elements")
+    n_y = 1 if epilogue == SKINNY_SWIGLU else len(weights)
+    if outs is None:
+        outs = [torch.empty(M, w8.shape[0], dtype=out_dtype, device=dev) for w8, _ in weights[:n_y]]
+    descs = (SkinnyFp8Out * max(1, len(weights)))()
+    for i, (w8, sw) in enumerate(weights):
+        if _bytes2d(w8, f"weight {i}").shape[1] != K:
+            raise RuntimeError(f"linear_skinny_fp8: weight {i} must be [N, {K}], got {tuple(w8.shape)}")
+        if sw.dtype != torch.float32 or sw.numel() != w8.shape[0] or not sw.is_contiguous():
+            raise RuntimeError(f"linear_skinny_fp8: scales of weight {i} must be contiguous fp32 [{w8.shape[0]}]")
+        descs[i].w8, descs[i].sw, descs[i].ldw, descs[i].N = w8.data_ptr(), sw.data_ptr(), w8.stride(0), w8.shape[0]
+        if i < n_y:
+            y = outs[i]
+            if tuple(y.shape) != (M, w8.shape[0]) or y.stride(1) != 1 or y.dtype != out_dtype or y.device != dev:
+                raise RuntimeError(f"linear_skinny_fp8: output {i} must be [{M}, {w8.shape[0]}] {out_dtype} on {dev}")
+            descs[i].y, descs[i].ldy = y.data_ptr(), y.stride(0)
+    _check(load().smt_linear_skinny_fp8(x8.data_ptr(), x8.stride(0), sx.data_ptr(), M, K, dt, descs, len(weights),
+                                        int(epilogue), None, _stream(dev)), "smt_linear_skinny_fp8")
     return list(outs)

@@ -14,6 +14,11 @@
 // and of W alone. Nothing here can wait for another workgroup.
 // SWIGLU: the workgroup streams the same 16 features of the gate and the up weight into two accumulators
 // and applies the SwiGLU forward of llama_kernels.hip to the two rounded products.
+//
+// skinny_fp8_kernel is the same stream on e4m3 bytes (smt_linear_skinny_fp8): a step is 64 K-elements, again
+// one 16-byte load per lane of W and of x (lane l: bytes k0 + 16 (l >> 4) + 0..15 of row l & 15), feeding two
+// v_mfma_f32_16x16x32_fp8_fp8 (the low and the high 8 bytes of both loads); wave 0 multiplies the summed
+// accumulator by RN32(sx[m] * sw[n]) before the one rounding.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -184,9 +189,137 @@ void skinny_kernel(const Params p) {
     *reinterpret_cast<uint2*>(yp) = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
 }
 
-const char* check_sizes(int32_t M, int32_t K, const SmtSkinnyOut* outs, int32_t n_out, int32_t epilogue) {
+
+// ---------------------------------------------------------------------------------------------- e4m3 operands
+struct Fp8Params {
+    const uint8_t* x;
+    int64_t ldx;
+    const float* sx;
+    const uint8_t* w[SMT_LINEAR_MAX_OUT];
+    const float* sw[SMT_LINEAR_MAX_OUT];
+    int64_t ldw[SMT_LINEAR_MAX_OUT];
+    uint16_t* y[SMT_LINEAR_MAX_OUT];
+    int64_t ldy[SMT_LINEAR_MAX_OUT];
+    int32_t tile_end[SMT_LINEAR_MAX_OUT];
+    int32_t M, K;
+};
+
+// load_batch on bytes: a step is 64 bytes of a row here too.
+template <int NW, int U>
+__device__ __forceinline__ void load_batch8(u32x4 (&a)[NW][U], u32x4 (&b)[U], const uint8_t* const (&wp)[NW],
+                                            const uint8_t* xp, int s, int s_end) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t off = (int64_t)min(s + u, s_end - 1) * 64;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) a[i][u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wp[i] + off));
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) b[u] = *reinterpret_cast<const u32x4*>(xp + (int64_t)min(s + u, s_end - 1) * 64);
+}
+
+// one step: the low 8 bytes of both operands, then the high 8
+__device__ __forceinline__ f32x4 mfma8(const u32x4 a, const u32x4 b, f32x4 c) {
+    using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
+    c = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(__builtin_bit_cast(long, u32x2{a.x, a.y}),
+                                                   __builtin_bit_cast(long, u32x2{b.x, b.y}), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(__builtin_bit_cast(long, u32x2{a.z, a.w}),
+                                                      __builtin_bit_cast(long, u32x2{b.z, b.w}), c, 0, 0, 0);
+}
+
+// F: the output dtype. The schedule is skinny_kernel's.
+template <int F, int NW, int U>
+__global__ __launch_bounds__(THREADS)
+void skinny_fp8_kernel(const Fp8Params p) {
+    __shared__ f32x4 part[NW][WAVES][64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 15, h = lane >> 4;
+
+    int out = 0, tile = blockIdx.x;
+    if constexpr (NW == 1) {
+        out = (tile >= p.tile_end[0]) + (tile >= p.tile_end[1]);
+        if (out) tile -= p.tile_end[out - 1];
+    }
+    const int n0 = tile * 16;
+    const uint8_t* wp[NW];
+    if constexpr (NW == 1) wp[0] = p.w[out] + (int64_t)(n0 + r) * p.ldw[out] + 16 * h;
+    else {
+        wp[0] = p.w[0] + (int64_t)(n0 + r) * p.ldw[0] + 16 * h;
+        wp[1] = p.w[1] + (int64_t)(n0 + r) * p.ldw[1] + 16 * h;
+    }
+    const bool row_live = r < p.M;                  // rows >= M: row 0's bytes, the column is dropped
+    const uint8_t* xp = p.x + (int64_t)(row_live ? r : 0) * p.ldx + 16 * h;
+
+    const int steps = p.K >> 6;
+    const int per = (steps + WAVES - 1) / WAVES;
+    const int s = wave * per;
+    const int s_end = min(steps, s + per);
+
+    f32x4 acc[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int n = s_end - s;
+    const int nb = (n + U - 1) / U;
+    if (nb > 0) {
+        u32x4 a[NW][U], b[U];
+        load_batch8<NW, U>(a, b, wp, xp, s, s_end);
+        for (int i = 1; i < nb; ++i) {
+            u32x4 an[NW][U], bn[U];
+            load_batch8<NW, U>(an, bn, wp, xp, s + i * U, s_end);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j) { acc[j] = mfma8(a[j][u], b[u], acc[j]); a[j][u] = an[j][u]; }
+                b[u] = bn[u];
+            }
+        }
+        const int left = n - (nb - 1) * U;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (u < left) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j) acc[j] = mfma8(a[j][u], b[u], acc[j]);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int i = 0; i < NW; ++i) part[i][wave][lane] = acc[i];
+    __syncthreads();
+    if (wave != 0 || !row_live) return;
+
+    // lane l: features n0 + 4 (l >> 4) + 0..3 of row l & 15; sx of a live row only
+    const float sx = p.sx[r];
+    f32x4 v[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        f32x4 sum = part[i][0][lane];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) sum += part[i][w][lane];
+        const f32x4 sw = *reinterpret_cast<const f32x4*>(p.sw[NW == 1 ? out : i] + n0 + 4 * h);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[i][j] = sum[j] * (sx * sw[j]);
+    }
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if constexpr (NW == 1) o[j] = f2u<F>(v[0][j]);
+        else {
+            const float g = rnd<F>(v[0][j]), up = rnd<F>(v[1][j]);
+            const float sg = rnd<F>(g * smt_sigmoid(g));
+            o[j] = f2u<F>(sg * up);
+        }
+    }
+    uint16_t* yp = (NW == 1 ? p.y[out] + (int64_t)r * p.ldy[out] : p.y[0] + (int64_t)r * p.ldy[0]) + n0 + 4 * h;
+    *reinterpret_cast<uint2*>(yp) = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+}
+
+// KSTEP: the K-elements of one step, 32 (16-bit operands) or 64 (bytes)
+template <int KSTEP, typename Out>
+const char* check_sizes(int32_t M, int32_t K, const Out* outs, int32_t n_out, int32_t epilogue) {
     if (M < 1 || M > SMT_LINEAR_MAX_M) return "M must lie in [1, 16]";
-    if (K < 32 || (K & 31)) return "K must be a positive multiple of 32";
+    if (K < KSTEP || (K % KSTEP)) return KSTEP == 32 ? "K must be a positive multiple of 32" : "K must be a positive multiple of 64";
     if (epilogue != SMT_SKINNY_PLAIN && epilogue != SMT_SKINNY_SWIGLU) return "unknown epilogue";
     if (n_out < 1 || n_out > SMT_LINEAR_MAX_OUT) return "n_out must lie in [1, 3]";
     if (!outs) return "null outs";
@@ -211,6 +344,17 @@ int launch(const Params& p, int32_t epilogue, uint32_t grid, hipStream_t stream)
     return 0;
 }
 
+template <int F>
+int launch_fp8(const Fp8Params& p, int32_t epilogue, uint32_t grid, hipStream_t stream) {
+    if (epilogue == SMT_SKINNY_SWIGLU)
+        hipLaunchKernelGGL((skinny_fp8_kernel<F, 2, 4>), dim3(grid), dim3(THREADS), 0, stream, p);
+    else
+        hipLaunchKernelGGL((skinny_fp8_kernel<F, 1, 8>), dim3(grid), dim3(THREADS), 0, stream, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(-4, "smt_linear_skinny_fp8: %s", hipGetErrorString(e));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -218,14 +362,14 @@ extern "C" {
 const char* smt_linear_last_error(void) { return g_err; }
 
 int64_t smt_linear_skinny_workspace(int32_t M, int32_t K, const SmtSkinnyOut* outs, int32_t n_out, int32_t epilogue) {
-    if (const char* why = check_sizes(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny_workspace: %s", why);
+    if (const char* why = check_sizes<32>(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny_workspace: %s", why);
     return 0;
 }
 
 int smt_linear_skinny(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t dtype, const SmtSkinnyOut* outs,
                       int32_t n_out, int32_t epilogue, void* workspace, hipStream_t stream) {
     (void)workspace;
-    if (const char* why = check_sizes(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny: %s", why);
+    if (const char* why = check_sizes<32>(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny: %s", why);
     if (dtype != SMT_DTYPE_BF16 && dtype != SMT_DTYPE_FP16)
         return fail(-1, "smt_linear_skinny: dtype %d is not SMT_DTYPE_BF16 / _FP16", (int)dtype);
     const int n_y = epilogue == SMT_SKINNY_SWIGLU ? 1 : n_out;
@@ -260,6 +404,58 @@ int smt_linear_skinny(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t 
     const uint32_t grid = (uint32_t)(epilogue == SMT_SKINNY_SWIGLU ? outs[0].N / 16 : tiles);
     if (dtype == SMT_DTYPE_BF16) return launch<SMT_DTYPE_BF16>(p, epilogue, grid, stream);
     return launch<SMT_DTYPE_FP16>(p, epilogue, grid, stream);
+}
+
+int64_t smt_linear_skinny_fp8_workspace(int32_t M, int32_t K, const SmtSkinnyFp8Out* outs, int32_t n_out,
+                                        int32_t epilogue) {
+    if (const char* why = check_sizes<64>(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny_fp8_workspace: %s", why);
+    return 0;
+}
+
+int smt_linear_skinny_fp8(const void* x8, int64_t ldx, const float* sx, int32_t M, int32_t K, int32_t out_dtype,
+                          const SmtSkinnyFp8Out* outs, int32_t n_out, int32_t epilogue, void* workspace,
+                          hipStream_t stream) {
+    (void)workspace;
+    if (const char* why = check_sizes<64>(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny_fp8: %s", why);
+    if (out_dtype != SMT_DTYPE_BF16 && out_dtype != SMT_DTYPE_FP16)
+        return fail(-1, "smt_linear_skinny_fp8: out_dtype %d is not SMT_DTYPE_BF16 / _FP16", (int)out_dtype);
+    const int n_y = epilogue == SMT_SKINNY_SWIGLU ? 1 : n_out;
+    if (!x8 || !sx) return fail(-1, "smt_linear_skinny_fp8: null x8 or sx");
+    if (ldx < K) return fail(-1, "smt_linear_skinny_fp8: ldx %lld < K %d", (long long)ldx, (int)K);
+    for (int i = 0; i < n_out; ++i) {
+        if (!outs[i].w8 || !outs[i].sw || (i < n_y && !outs[i].y))
+            return fail(-1, "smt_linear_skinny_fp8: null w8, sw or y of output %d", i);
+        if (outs[i].ldw < K || (i < n_y && outs[i].ldy < outs[i].N))
+            return fail(-1, "smt_linear_skinny_fp8: ldw or ldy of output %d below its extent", i);
+    }
+    if (!aligned16(x8) || (ldx & 15) || (reinterpret_cast<uintptr_t>(sx) & 3u))
+        return fail(-2, "smt_linear_skinny_fp8: x8 must be 16-byte aligned, ldx %lld a multiple of 16, sx 4-byte aligned", (long long)ldx);
+    for (int i = 0; i < n_out; ++i) {
+        if (!aligned16(outs[i].w8) || !aligned16(outs[i].sw) || (outs[i].ldw & 15) ||
+            (i < n_y && (!aligned16(outs[i].y) || (outs[i].ldy & 7))))
+            return fail(-2, "smt_linear_skinny_fp8: w8, sw, y of output %d must be 16-byte aligned, ldw a multiple of 16, ldy of 8", i);
+    }
+    Fp8Params p = {};
+    p.x = static_cast<const uint8_t*>(x8);
+    p.ldx = ldx;
+    p.sx = sx;
+    p.M = M;
+    p.K = K;
+    int32_t tiles = 0;
+    for (int i = 0; i < SMT_LINEAR_MAX_OUT; ++i) {
+        if (i < n_out) {
+            p.w[i] = static_cast<const uint8_t*>(outs[i].w8);
+            p.sw[i] = outs[i].sw;
+            p.ldw[i] = outs[i].ldw;
+            p.y[i] = static_cast<uint16_t*>(outs[i].y);
+            p.ldy[i] = outs[i].ldy;
+            tiles += outs[i].N / 16;
+        }
+        p.tile_end[i] = tiles;
+    }
+    const uint32_t grid = (uint32_t)(epilogue == SMT_SKINNY_SWIGLU ? outs[0].N / 16 : tiles);
+    if (out_dtype == SMT_DTYPE_BF16) return launch_fp8<SMT_DTYPE_BF16>(p, epilogue, grid, stream);
+    return launch_fp8<SMT_DTYPE_FP16>(p, epilogue, grid, stream);
 }
 
 }  // extern "C"

@@ -22,7 +22,11 @@ copy, its log-softmax and its fp32 gradient are never materialised (tests/test_g
 ``patch_llama(decode_linears=True)`` (opt-in) routes the dense linears of a decode step (at most 16 rows,
 gradients off) to a weight-streaming kernel (``csrc/linear_kernels.hip``, C ABI ``include/smt_linear.h``;
 :func:`decode_linear`, :func:`decode_linear_group`, :func:`decode_swiglu`) at the sizes where it measured
-faster than hipBLASLt (tests/test_gpu_decode_linear.py, tests/test_gpu_generate_decode_linears.py).
+faster than hipBLASLt (tests/test_gpu_decode_linear.py, tests/test_gpu_generate_decode_linears.py). With
+``decode_fp8=True`` as well, the frozen linears of an fp8 model (``engine.attach_fp8_weights``) first try the
+same stream on their e4m3 bytes (``smt_linear_skinny_fp8``; :func:`decode_linear_fp8`,
+:func:`decode_linear_group_fp8`, :func:`decode_swiglu_fp8`) at the sizes where it measured faster than
+``quant_rows`` + ``torch._scaled_mm`` (tests/test_gpu_decode_linear_fp8.py, tests/test_gpu_generate_decode_fp8.py).
 
 The model's dtype is bf16 or, since ABI v13, fp16 (the reference's ``--dtype fp16``,
 ``fine_tune.py:955-959``): every kernel is one template body for both formats, rounding where the eager
@@ -602,8 +606,156 @@ def decode_swiglu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor) -> 
     return y
 
 
+# ------------------------------------------------------------------------------------------------
+# decode linears on e4m3 operands (opt-in: patch_llama(decode_linears=True, decode_fp8=True))
+# ------------------------------------------------------------------------------------------------
+class DecodeFp8Stats:
+    """Launches of the e4m3 decode-linear kernel by kind, and ``quant``: the activation quantisations
+    (smt_quant_rows_e4m3) those calls had to launch themselves because no producer had left the copy on the
+    tensor (o_proj's and down_proj's input). A graph replay runs no Python and counts nothing."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.single = 0
+        self.group = 0
+        self.swiglu = 0
+        self.quant = 0
+
+    def as_dict(self) -> dict:
+        return {"single": self.single, "group": self.group, "swiglu": self.swiglu, "quant": self.quant}
+
+
+decode_fp8_stats = DecodeFp8Stats()
+# The fp8 routing's size rule (read at call time; DECODE_FP8_RULE = False sends every qualifying launch to the
+# kernel, which scripts/generate_cache_bench.py uses to time the token without the rule). A launch goes to the
+# kernel only if K <= 4096 and its e4m3 weights (sum of N times K bytes) hold at most 2^25 bytes at any number of
+# rows, or at most 2^27 bytes at up to 4 rows. Measured against today's route (fp8.quant_rows where the copy is
+# not there, torch._scaled_mm per weight) at M = 1, 4, 16 (profiles/r21_decode_linear_fp8_bench.jsonl, DESIGN 4c):
+# inside the rule, (N, K) = (4096, 4096), (1024, 4096), the grouped (6144, 4096) and o_proj with its quantisation
+# launch are 1.32-3.48x faster at every M, (14336, 4096) and the SwiGLU pair 1.37-1.83x at M = 1 and 4, each in
+# every round with a margin far above the baseline's spread; outside it, (14336, 4096) at M = 16 (0.74x), the pair
+# at M = 16 (1.05x in the recorded run, 0.98x in the run before it: a margin that changes sign between two runs),
+# K = 14336 (0.87-1.03x, inside the spread where above 1) and the 13B shapes (0.42-0.75x; 13b.gate at M <= 4 was
+# 1.05-1.11x, which the K limit gives up) keep today's route.
+DECODE_FP8_RULE = True
+DECODE_FP8_MAX_K = 4096
+DECODE_FP8_MAX_WEIGHT_BYTES = 1 << 25
+DECODE_FP8_FEW_ROWS = 4
+DECODE_FP8_MAX_WEIGHT_BYTES_FEW_ROWS = 1 << 27
+
+
+def _fp8_copy(w):
+    """The Fp8Weight of ``w``: ``w`` itself, or the copy a weight tensor carries as ``_smt_fp8``; None if neither."""
+    fw = getattr(w, "_smt_fp8", w)
+    return fw if hasattr(fw, "w8") and hasattr(fw, "sw") else None
+
+
+def decode_linear_fp8_reason(x: torch.Tensor, fws, biases=(), need_cuda: bool = True):
+    """Why ``x @ W^T`` on the e4m3 copies ``fws`` (``Fp8Weight``s, or weights that carry one as ``_smt_fp8``)
+    cannot go to smt_linear_skinny_fp8, or None if it can: gradients off; a ROCm bf16 activation of 1..16
+    rows (bf16 only: the row quantiser smt_quant_rows_e4m3 reads nothing else, although the kernel itself also
+    writes fp16); every weight with its e4m3 copy; no bias; K % 64 == 0, N % 16 == 0; w8 with unit inner
+    stride, a row stride that is a multiple of 16 and 16-byte aligned storage, contiguous fp32 scales. The
+    strides of ``x`` do not matter: the kernel reads its e4m3 copy (``fp8.quant_rows_cached``), which is
+    contiguous. ``need_cuda=False`` lifts the device condition."""
+    if torch.is_grad_enabled():
+        return "gradients are enabled"
+    if any(b is not None for b in biases):
+        return "bias"
+    if x.dtype != torch.bfloat16:
+        return f"dtype {x.dtype} (the e4m3 row quantiser reads bf16)"
+    if need_cuda and x.device.type != "cuda":
+        return f"device {x.device}"
+    if x.dim() < 1 or x.shape[-1] == 0:
+        return "x has no feature dimension"
+    K = x.shape[-1]
+    rows = x.numel() // K
+    if not 1 <= rows <= _hip.SKINNY_MAX_M:
+        return f"{rows} rows"
+    if K % 64:
+        return f"K {K} is not a multiple of 64"
+    if not 1 <= len(fws) <= _hip.SKINNY_MAX_OUT:
+        return f"{len(fws)} weights"
+    for w in fws:
+        fw = _fp8_copy(w)
+        if fw is None:
+            return "weight without an fp8 copy"
+        w8, sw = fw.w8, fw.sw
+        if w8.dim() != 2 or w8.shape[1] != K or w8.element_size() != 1:
+            return f"w8 shape {tuple(w8.shape)} {w8.dtype} for K {K}"
+        if w8.device != x.device or sw.device != x.device:
+            return f"fp8 weight on {w8.device} beside x on {x.device}"
+        if w8.shape[0] == 0 or w8.shape[0] % 16:
+            return f"N {w8.shape[0]} is not a multiple of 16"
+        if w8.stride(1) != 1 or w8.stride(0) % 16 or w8.stride(0) < K or not _aligned16(w8):
+            return "w8 stride or alignment"
+        if sw.dtype != torch.float32 or sw.numel() != w8.shape[0] or not sw.is_contiguous() or not _aligned16(sw):
+            return "sw is not a contiguous, 16-byte aligned fp32 vector of N scales"
+    return None
+
+
+def _decode_fp8_routes(x, weights, biases=(), need_cuda: bool = True) -> bool:
+    """The fp8 routing's decision for one launch: :func:`decode_linear_fp8_reason` admits it and, unless
+    ``DECODE_FP8_RULE`` is off, the size rule holds."""
+    if decode_linear_fp8_reason(x, weights, biases, need_cuda) is not None:
+        return False
+    if not DECODE_FP8_RULE:
+        return True
+    K = x.shape[-1]
+    limit = DECODE_FP8_MAX_WEIGHT_BYTES_FEW_ROWS if x.numel() // K <= DECODE_FP8_FEW_ROWS else DECODE_FP8_MAX_WEIGHT_BYTES
+    return K <= DECODE_FP8_MAX_K and sum(_fp8_copy(w).w8.shape[0] for w in weights) * K <= limit
+
+
+def _decode_fp8_call(x, fws, epilogue, what):
+    why = decode_linear_fp8_reason(x, fws)
+    if why is not None:                 # no quiet fall-back: the routing asks the predicate first
+        raise RuntimeError(f"{what}: the call does not qualify for the e4m3 decode-linear kernel ({why})")
+    fws = [_fp8_copy(w) for w in fws]
+    if epilogue == _hip.SKINNY_SWIGLU and fws[0].w8.shape[0] != fws[1].w8.shape[0]:
+        raise RuntimeError(f"{what}: gate and up of unequal width")
+    from .fp8 import quant_rows_cached
+    c = x.__dict__.get("_smt_q8")
+    if c is None or c[0] != x._version:
+        decode_fp8_stats.quant += 1
+    x8, sx = quant_rows_cached(x)
+    ys = _hip.linear_skinny_fp8(x8, sx, [(fw.w8, fw.sw) for fw in fws], x.dtype, epilogue)
+    return [y.view(*x.shape[:-1], y.shape[-1]) for y in ys]
+
+
+def decode_linear_fp8(x: torch.Tensor, fw) -> torch.Tensor:
+    """``x @ W^T`` for at most 16 rows of a bf16 ``x`` on the e4m3 copy ``fw`` (an ``Fp8Weight``) of ``W``: one
+    launch of the weight-streaming kernel (smt_linear_skinny_fp8) on ``fw.w8`` / ``fw.sw`` as they are at the
+    call, and on the e4m3 copy of ``x`` that ``fp8.quant_rows_cached`` returns (the one the fused RMSNorm left
+    on ``x``, else one smt_quant_rows_e4m3 launch). An error if the call does not qualify
+    (:func:`decode_linear_fp8_reason`). No CPU path: the fp8 path has none."""
+    y = _decode_fp8_call(x, (fw,), _hip.SKINNY_PLAIN, "decode_linear_fp8")[0]
+    decode_fp8_stats.single += 1
+    return y
+
+
+def decode_linear_group_fp8(x: torch.Tensor, fws) -> list:
+    """``[x @ W^T for W in ...]`` on 1..3 e4m3 copies as one launch that reads the e4m3 ``x`` once; bit for bit
+    the single calls."""
+    ys = _decode_fp8_call(x, tuple(fws), _hip.SKINNY_PLAIN, "decode_linear_group_fp8")
+    decode_fp8_stats.group += 1
+    return ys
+
+
+def decode_swiglu_fp8(x: torch.Tensor, fw_gate, fw_up) -> torch.Tensor:
+    """``silu(x @ W_gate^T) * (x @ W_up^T)`` on the e4m3 copies as one launch; bit for bit two
+    :func:`decode_linear_fp8` calls and the fused SwiGLU forward."""
+    y = _decode_fp8_call(x, (fw_gate, fw_up), _hip.SKINNY_SWIGLU, "decode_swiglu_fp8")[0]
+    decode_fp8_stats.swiglu += 1
+    return y
+
+
 def _sync_for_decode(*mods) -> None:
-    """The SMT modules' write-back of their tiles into W, as their own forward does first."""
+    """The SMT modules' write-back of their tiles into W, as their own forward does first. ``sync_weight``
+    also re-quantises the rows and columns of the e4m3 copies that the tiles touch (``Fp8Weight.refresh``), as
+    the module's own forward does at that point, so the fp8 route needs nothing more: after it ``w8`` holds
+    the rows the module's forward would use."""
     for m in mods:
         if getattr(m, "writeback_on_forward", False) and hasattr(m, "sync_weight"):
             m.sync_weight()
@@ -632,16 +784,25 @@ def decode_routed_linear_forward(self, x):
         else:
             del x.__dict__["_smt_decode_kv"]
     bias = getattr(self, "bias", None)
+    fp8 = self.__dict__.get("_smt_decode_fp8", False)
     group = self.__dict__.get("_smt_decode_group")
     if group is not None and DECODE_LINEAR_GROUP:
         kv = [r() for r in group]
         if all(m is not None for m in kv):
             ws = (self.weight, kv[0].weight, kv[1].weight)
+            if fp8 and _decode_fp8_routes(x, ws, (bias, kv[0].bias, kv[1].bias)):
+                _sync_for_decode(self, *kv)
+                q, k, v = decode_linear_group_fp8(x, ws)
+                x.__dict__["_smt_decode_kv"] = [x._version, ws[1], k, ws[2], v]
+                return q
             if _decode_routes(x, ws, (bias, kv[0].bias, kv[1].bias)):
                 _sync_for_decode(self, *kv)
                 q, k, v = decode_linear_group(x, ws)
                 x.__dict__["_smt_decode_kv"] = [x._version, ws[1], k, ws[2], v]
                 return q
+    if fp8 and _decode_fp8_routes(x, (self.weight,), (bias,)):
+        _sync_for_decode(self)
+        return decode_linear_fp8(x, self.weight)
     if _decode_routes(x, (self.weight,), (bias,)):
         _sync_for_decode(self)
         return decode_linear(x, self.weight)
@@ -667,11 +828,14 @@ def _unroute_decode_linear(m) -> None:
         if prev is not None:
             m.__dict__["forward"] = prev
     m.__dict__.pop("_smt_decode_group", None)
+    m.__dict__.pop("_smt_decode_fp8", None)
 
 
-def route_decode_linears(model: nn.Module) -> int:
+def route_decode_linears(model: nn.Module, fp8: bool = False) -> int:
     """What ``patch_llama(decode_linears=True)`` adds, by itself: the routed forwards of the projections
-    and of a bias-free ``lm_head``, the q/k/v group and the MLPs' fused launch. Returns the number of linears
+    and of a bias-free ``lm_head``, the q/k/v group and the MLPs' fused launch. ``fp8``
+    (``patch_llama(decode_fp8=True)``): the routed forwards and the MLPs first try the e4m3 kernel on weights
+    that carry an fp8 copy. Returns the number of linears
     routed by this call. :func:`unroute_decode_linears` (and :func:`unpatch_llama`) removes all of it."""
     ml = _ml()
     routed = 0
@@ -681,6 +845,8 @@ def route_decode_linears(model: nn.Module) -> int:
         elif isinstance(m, ml.LlamaMLP):
             names = ("gate_proj", "up_proj", "down_proj")
             m.__dict__["_smt_decode_linears"] = True
+            if fp8:
+                m.__dict__["_smt_decode_fp8"] = True
         elif isinstance(m, ml.LlamaForCausalLM):
             names = ("lm_head",) if getattr(getattr(m, "lm_head", None), "bias", None) is None else ()
         else:
@@ -690,6 +856,8 @@ def route_decode_linears(model: nn.Module) -> int:
             if lin is not None and _decode_routable(lin):
                 _route_decode_linear(lin)
                 routed += 1
+            if fp8 and lin is not None and lin.__dict__.get("_smt_decode_routed"):
+                lin.__dict__["_smt_decode_fp8"] = True
         if isinstance(m, ml.LlamaAttention) and all(
                 getattr(m, n, None) is not None and getattr(m, n).__dict__.get("_smt_decode_routed") for n in names[:3]):
             m.q_proj.__dict__["_smt_decode_group"] = (weakref.ref(m.k_proj), weakref.ref(m.v_proj))
@@ -699,6 +867,7 @@ def route_decode_linears(model: nn.Module) -> int:
 def unroute_decode_linears(model: nn.Module) -> None:
     for m in model.modules():
         m.__dict__.pop("_smt_decode_linears", None)
+        m.__dict__.pop("_smt_decode_fp8", None)
         _unroute_decode_linear(m)
 
 
@@ -709,10 +878,13 @@ def fused_mlp_forward(self, x):
         # patch_llama(decode_linears=True): gate, up and the SwiGLU of a decode step as one launch
         g, u = self.gate_proj, self.up_proj
         if (g.__dict__.get("_smt_decode_routed") and u.__dict__.get("_smt_decode_routed")
-                and g.weight.shape[0] == u.weight.shape[0]
-                and _decode_routes(x, (g.weight, u.weight), (g.bias, u.bias))):
-            _sync_for_decode(g, u)
-            return self.down_proj(decode_swiglu(x, g.weight, u.weight))
+                and g.weight.shape[0] == u.weight.shape[0]):
+            if self.__dict__.get("_smt_decode_fp8") and _decode_fp8_routes(x, (g.weight, u.weight), (g.bias, u.bias)):
+                _sync_for_decode(g, u)
+                return self.down_proj(decode_swiglu_fp8(x, g.weight, u.weight))
+            if _decode_routes(x, (g.weight, u.weight), (g.bias, u.bias)):
+                _sync_for_decode(g, u)
+                return self.down_proj(decode_swiglu(x, g.weight, u.weight))
     from .fp8 import sole_swiglu_consumer
     with sole_swiglu_consumer():             # gate / up feed only the SwiGLU below
         gate, up = self.gate_proj(x), self.up_proj(x)
@@ -1867,7 +2039,7 @@ def _keep_2d_mask(config=None, inputs_embeds=None, attention_mask=None, **kwargs
 
 
 def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_head_loss: bool = None,
-                decode_linears: bool = False) -> dict:
+                decode_linears: bool = False, decode_fp8: bool = False) -> dict:
     """Route a transformers LLaMA model's RMSNorm / RoPE / SwiGLU / attention-residual add (and, with ``attention``, its
     attention; with ``loss``, its causal-LM loss) through the fused kernels. RoPE is patched at
     module level (``modeling_llama.apply_rotary_pos_emb``, looked up by ``LlamaAttention.forward`` at
@@ -1889,7 +2061,13 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
     ``DECODE_LINEAR_MAX_K`` and the launch's weights within ``DECODE_LINEAR_MAX_WEIGHT_ELEMS`` (the shapes at
     which the kernel measured faster than hipBLASLt); every
     other call runs what it ran before.
+    ``decode_fp8`` (off by default, needs ``decode_linears``; without it no code path changes): on weights that
+    carry an e4m3 copy (``engine.attach_fp8_weights``) the routed forwards first try the e4m3 weight-streaming
+    kernel (smt_linear_skinny_fp8) where :func:`decode_linear_fp8_reason` admits the call and the
+    ``DECODE_FP8_*`` size rule holds, and then fall through to what they do without it.
     Returns counts of patched modules (with ``decode_linears``, also the routed linears). Idempotent."""
+    if decode_fp8 and not decode_linears:
+        raise ValueError("patch_llama(decode_fp8=True) needs decode_linears=True: the fp8 route is part of that routing")
     ml = _ml()
     counts = {"rmsnorm": 0, "mlp": 0, "rope": 1, "attention": 0, "loss": 0, "decoder": 0, "lm_head_loss": 0}
     if lm_head_loss is None:
@@ -1944,7 +2122,7 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
                 m[i].__dict__["_smt_next_layer"] = weakref.ref(m[i + 1])
     ml.apply_rotary_pos_emb = fused_apply_rotary_pos_emb
     if decode_linears:
-        counts["decode_linears"] = route_decode_linears(model)
+        counts["decode_linears"] = route_decode_linears(model, fp8=decode_fp8)
     return counts
 
 
