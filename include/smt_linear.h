@@ -67,6 +67,28 @@ int smt_linear_skinny(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t 
                       int32_t n_out, int32_t epilogue, void* workspace, hipStream_t stream);
 
 /*
+ * smt_linear_skinny with a bias per output (the q, k and v projections of a Qwen2 model):
+ *
+ *     y[m][n] = RN_out( acc[m][n] + (float)b[n] ),
+ *
+ * acc the sum of the SMT_LINEAR_KSPLIT partials in wave order, as above; the add is one fp32 add in wave 0 and
+ * the store's rounding is the only rounding to the dtype.
+ * biases: HOST array of n_out device pointers. biases[i] is NULL (output i has no bias: its y is bit for bit
+ * smt_linear_skinny's) or points to b [N_i] of the call's dtype, 16-byte aligned, unit stride. A workgroup reads
+ * the 16 features of its tile once (32 bytes, wave 0, default cache policy).
+ * SMT_SKINNY_PLAIN only: SMT_SKINNY_SWIGLU with any non-NULL entry returns -1. With every entry NULL the call
+ * is smt_linear_skinny's launch, either epilogue.
+ * Everything else is smt_linear_skinny's contract: a row's output is a function of that row of x, of W and of
+ * b alone; rows >= M of x are never read; nothing of y is written outside [0, M) x [0, N); no synchronisation
+ * between workgroups, workspace 0 (smt_linear_skinny_workspace answers for this call too); one launch, no
+ * allocation, launch parameters from shapes and pointers only, so a captured call replays; the same return
+ * codes, with -1 for a NULL `biases` and -2 for a misaligned bias, before any HIP call.
+ */
+int smt_linear_skinny_bias(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t dtype, const SmtSkinnyOut* outs,
+                           const void* const* biases, int32_t n_out, int32_t epilogue, void* workspace,
+                           hipStream_t stream);
+
+/*
  * The same stream on e4m3 operands (the fp8 path's frozen linears): x8 [M][ldx] e4m3fn bytes with one fp32
  * scale per row, sx [M]; each of the 1..3 outputs w8 [N][ldw] e4m3fn bytes with one fp32 scale per output
  * feature, sw [N]: exactly what smt_quant_rows_e4m3 (smt_fp8.h) writes. y is bf16 or fp16 (`out_dtype`).

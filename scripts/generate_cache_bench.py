@@ -31,6 +31,11 @@ rule, every qualifying launch on the kernel). The routing is put on and taken of
 the modules as ``patch_llama(model)`` leaves them. The ratio line carries
 ``seconds_graph_over_<variant>`` per loop.
 
+``--model qwen2-7b`` builds a random-weight Qwen2ForCausalLM of the 7B DeepSeek-R1 distill's shape (28 layers, hidden
+3584, Hq 28, Hkv 4, intermediate 18944, vocabulary 152064; q, k and v with a bias) in place of the bench.py model;
+every model is patched with ``patch_model``. The ``nobias`` variant of ``--decode-linears`` is ``all`` with the bias
+routing off (``DECODE_LINEAR_BIAS``): biased projections then run what they run without the flag.
+
 ``--fp8`` adds, for every ``beam_shared_graph`` leg, three legs on a second model of the same weights, frozen,
 with ``engine.attach_fp8_weights`` (config 5): ``fp8_base`` = that model as ``patch_llama(model)`` leaves it
 (``fp8.quant_rows`` + ``torch._scaled_mm`` per projection: the baseline of the other two), ``fp8`` = with
@@ -50,20 +55,44 @@ from bench import MODELS, build_model  # noqa: E402
 from sparse_matrix_tuning_amd import beam_search  # noqa: E402
 from sparse_matrix_tuning_amd.beam_cache import BeamSharedCache  # noqa: E402
 from sparse_matrix_tuning_amd import fused_llama  # noqa: E402
-from sparse_matrix_tuning_amd.fused_llama import DecodeGraph, patch_llama  # noqa: E402
+from sparse_matrix_tuning_amd.fused_llama import DecodeGraph, patch_model  # noqa: E402
+
+QWEN2 = {"qwen2-7b": dict(vocab_size=152064, hidden_size=3584, intermediate_size=18944, num_hidden_layers=28,
+                          num_attention_heads=28, num_key_value_heads=4, rope_theta=10000.0, rms_norm_eps=1e-6,
+                          max_position_embeddings=8192, tie_word_embeddings=False, initializer_range=0.02)}
 
 DL_RULE, DL_MAX_K = fused_llama.DECODE_LINEAR_MAX_WEIGHT_ELEMS, fused_llama.DECODE_LINEAR_MAX_K
 # variant: (q/k/v as one launch, gate/up/SwiGLU as one launch, the size rule's limit)
 DL_VARIANTS = {"all": (True, True, DL_RULE), "single": (False, False, DL_RULE), "nogroup": (False, True, DL_RULE),
                "noswiglu": (True, False, DL_RULE), "unbounded": (True, True, 1 << 62),
                "unbounded_single": (False, False, 1 << 62), "unbounded_nogroup": (False, True, 1 << 62),
-               "unbounded_noswiglu": (True, False, 1 << 62)}
+               "unbounded_noswiglu": (True, False, 1 << 62), "nobias": (True, True, DL_RULE)}
 FP8_VARIANTS = {"fp8_base": None, "fp8": True, "fp8_unbounded": False}      # variant: DECODE_FP8_RULE (None: unrouted)
+
+
+def build_qwen2(name, device):
+    """bench.build_model's recipe for a Qwen2 shape; the q/k/v biases, which transformers zeroes, are drawn too."""
+    from transformers import Qwen2Config, Qwen2ForCausalLM
+    cfg = Qwen2Config(**QWEN2[name])
+    cfg._attn_implementation = "sdpa"
+    torch.manual_seed(1234)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.bfloat16)
+    try:
+        with torch.device(device):
+            model = Qwen2ForCausalLM(cfg)
+    finally:
+        torch.set_default_dtype(prev)
+    with torch.no_grad():
+        for n, p in model.named_parameters():
+            if n.endswith("_proj.bias"):
+                p.normal_(0.0, 0.02)
+    return model
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="llama3-8b", choices=sorted(MODELS))
+    ap.add_argument("--model", default="llama3-8b", choices=sorted(MODELS) + sorted(QWEN2))
     ap.add_argument("--prompts", type=int, default=4)
     ap.add_argument("--beams", type=int, default=4)
     ap.add_argument("--prompt-len", type=int, default=256)
@@ -83,9 +112,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("generate_cache_bench: needs the GPU")
     dev = torch.device("cuda", 0)
-    model = build_model(a.model, dev).eval()
+    if a.fp8 and a.model in QWEN2:
+        raise SystemExit("generate_cache_bench: --fp8 runs on the bench.py models")
+    model = (build_qwen2 if a.model in QWEN2 else build_model)(a.model, dev).eval()
     model.generation_config.pad_token_id = 0
-    patch_llama(model)
+    patch_model(model)
     fp8_model = None
     if a.fp8:
         from sparse_matrix_tuning_amd import engine
@@ -94,9 +125,9 @@ def main():
         for p in fp8_model.parameters():
             p.requires_grad_(False)
         engine.attach_fp8_weights(fp8_model)
-        patch_llama(fp8_model)
+        patch_model(fp8_model)
     g = torch.Generator().manual_seed(0)
-    ids = torch.randint(3, MODELS[a.model]["vocab_size"], (a.prompts, a.prompt_len), generator=g)
+    ids = torch.randint(3, model.config.vocab_size, (a.prompts, a.prompt_len), generator=g)
     mask = torch.ones_like(ids)
     for b in range(a.prompts):                             # left padding: 0, 1/8, 2/8, ... of the prompt
         pad = (b * a.prompt_len) // 8
@@ -150,6 +181,7 @@ def main():
                     (fused_llama.DECODE_LINEAR_GROUP, fused_llama.DECODE_LINEAR_SWIGLU,
                      fused_llama.DECODE_LINEAR_MAX_WEIGHT_ELEMS) = DL_VARIANTS[v]
                     fused_llama.DECODE_LINEAR_MAX_K = DL_MAX_K if DL_VARIANTS[v][2] == DL_RULE else 1 << 30
+                    fused_llama.DECODE_LINEAR_BIAS = v != "nobias"
                 routed["now"] = v
 
         def run(kw, v=None):
@@ -183,7 +215,8 @@ def main():
                         "ms_per_token": round(1e3 * s / new, 3), "shape": list(out.shape),
                         f"same_tokens_as_{first}": same[name]}
                 if a.decode_linears is not None or a.fp8:
-                    line.update(decode_linears=variant_of(name), routed_launches=fused_llama.decode_linear_stats.as_dict())
+                    line.update(decode_linears=variant_of(name), routed_launches=fused_llama.decode_linear_stats.as_dict(),
+                                biased_launches=fused_llama.decode_linear_stats.bias)
                     if variant_of(name) in FP8_VARIANTS:
                         line.update(fp8_launches=fused_llama.decode_fp8_stats.as_dict())
                     base = name.replace("@" + str(variant_of(name)), "@fp8_base" if variant_of(name) in FP8_VARIANTS else "")

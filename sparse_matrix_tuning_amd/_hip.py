@@ -54,7 +54,7 @@ ABI_FUNCTIONS = (
     "smt_rmsnorm_fwd_quant_e4m3",
     "smt_rmsnorm_bwd_add_quant_e4m3",
     "smt_beam_last_error", "smt_beam_topk_workspace", "smt_beam_topk",
-    "smt_linear_last_error", "smt_linear_skinny_workspace", "smt_linear_skinny",
+    "smt_linear_last_error", "smt_linear_skinny_workspace", "smt_linear_skinny", "smt_linear_skinny_bias",
     "smt_linear_skinny_fp8_workspace", "smt_linear_skinny_fp8",
 )
 
@@ -247,6 +247,8 @@ _SIGS = {
     "smt_linear_last_error": (ctypes.c_char_p, []),
     "smt_linear_skinny_workspace": (_I64, [_I32, _I32, ctypes.POINTER(SkinnyOut), _I32, _I32]),
     "smt_linear_skinny": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(SkinnyOut), _I32, _I32, _P, _P]),
+    "smt_linear_skinny_bias": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(SkinnyOut),
+                                              ctypes.POINTER(ctypes.c_void_p), _I32, _I32, _P, _P]),
     "smt_linear_skinny_fp8_workspace": (_I64, [_I32, _I32, ctypes.POINTER(SkinnyFp8Out), _I32, _I32]),
     "smt_linear_skinny_fp8": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _I32, ctypes.POINTER(SkinnyFp8Out), _I32, _I32, _P, _P]),
 }
@@ -909,12 +911,15 @@ def channel_scores(acc: torch.Tensor, strategy: int) -> torch.Tensor:
 
 
 def linear_skinny(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: int = SKINNY_PLAIN,
-                  outs: Optional[Sequence[torch.Tensor]] = None) -> list:
+                  outs: Optional[Sequence[torch.Tensor]] = None,
+                  biases: Optional[Sequence[Optional[torch.Tensor]]] = None) -> list:
     """``[x @ W_i^T for W_i in weights]`` for at most 16 rows of ``x [M, K]`` (smt_linear_skinny,
     include/smt_linear.h): one launch streams the 1..3 row-major ``[N_i, K]`` weights as they lie.
     ``SKINNY_SWIGLU``: two weights of equal N, one result ``swiglu(x @ W_0^T, x @ W_1^T)``.
-    ``outs``: the result buffers (``[M, N_i]``, unit inner stride), allocated if not given."""
-    dev = _require_device(x, *weights)
+    ``outs``: the result buffers (``[M, N_i]``, unit inner stride), allocated if not given.
+    ``biases`` (smt_linear_skinny_bias): one entry per weight, None or ``[N_i]`` of x's dtype with unit stride,
+    added in fp32 before the one rounding; ``SKINNY_PLAIN`` only. Without it the call is smt_linear_skinny's."""
+    dev = _require_device(x, *weights, *(biases or ()))
     dt = dtype_code16(x.dtype, "linear_skinny")
     if x.dim() != 2 or x.stride(1) != 1:
         raise RuntimeError(f"linear_skinny: x must be [M, K] with unit inner stride, got {tuple(x.shape)} / {x.stride()}")
@@ -933,6 +938,20 @@ def linear_skinny(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: in
             if tuple(y.shape) != (M, w.shape[0]) or y.stride(1) != 1 or y.dtype != x.dtype or y.device != dev:
                 raise RuntimeError(f"linear_skinny: output {i} must be [{M}, {w.shape[0]}] {x.dtype} on {dev}")
             descs[i].y, descs[i].ldy = y.data_ptr(), y.stride(0)
+    if biases is not None:
+        if len(biases) != len(weights):
+            raise RuntimeError(f"linear_skinny: {len(biases)} biases for {len(weights)} weights")
+        ptrs = (ctypes.c_void_p * max(1, len(weights)))()
+        for i, (b, w) in enumerate(zip(biases, weights)):
+            if b is None:
+                continue
+            if b.dim() != 1 or b.shape[0] != w.shape[0] or b.stride(0) != 1 or b.dtype != x.dtype:
+                raise RuntimeError(f"linear_skinny: bias {i} must be [{w.shape[0]}] {x.dtype} with unit stride, got "
+                                   f"{tuple(b.shape)} {b.dtype} / {b.stride()}")
+            ptrs[i] = b.data_ptr()
+        _check(load().smt_linear_skinny_bias(x.data_ptr(), x.stride(0), M, K, dt, descs, ptrs, len(weights),
+                                             int(epilogue), None, _stream(dev)), "smt_linear_skinny_bias")
+        return list(outs)
     _check(load().smt_linear_skinny(x.data_ptr(), x.stride(0), M, K, dt, descs, len(weights), int(epilogue), None,
                                     _stream(dev)), "smt_linear_skinny")
     return list(outs)

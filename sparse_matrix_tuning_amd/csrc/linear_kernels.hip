@@ -14,6 +14,9 @@
 // and of W alone. Nothing here can wait for another workgroup.
 // SWIGLU: the workgroup streams the same 16 features of the gate and the up weight into two accumulators
 // and applies the SwiGLU forward of llama_kernels.hip to the two rounded products.
+// Bias (smt_linear_skinny_bias, PLAIN): an instantiation of its own on BiasParams; wave 0 reads the 16 bias
+// features of its tile and adds them in fp32 to the summed accumulator before the one rounding. The plain
+// instantiations are compiled from the same text and keep their instructions (profiles/r22_isa_compare.txt).
 //
 // skinny_fp8_kernel is the same stream on e4m3 bytes (smt_linear_skinny_fp8): a step is 64 K-elements, again
 // one 16-byte load per lane of W and of x (lane l: bytes k0 + 16 (l >> 4) + 0..15 of row l & 15), feeding two
@@ -83,6 +86,13 @@ struct Params {
     int64_t ldy[SMT_LINEAR_MAX_OUT];
     int32_t tile_end[SMT_LINEAR_MAX_OUT];      // PLAIN: running count of 16-feature tiles over the outputs
     int32_t M, K;
+    static constexpr bool kBias = false;
+};
+
+// smt_linear_skinny_bias: the same, and one [N] bias of the dtype per output (NULL: none)
+struct BiasParams : Params {
+    const uint16_t* b[SMT_LINEAR_MAX_OUT];
+    static constexpr bool kBias = true;
 };
 
 // Steps [s, s + U) of a slice that ends at s_end, a step past the end replaced by the slice's last one (its
@@ -101,10 +111,12 @@ __device__ __forceinline__ void load_batch(u32x4 (&a)[NW][U], u32x4 (&b)[U], con
     for (int u = 0; u < U; ++u) b[u] = *reinterpret_cast<const u32x4*>(xp + (int64_t)min(s + u, s_end - 1) * 32);
 }
 
-// NW weight streams (1: PLAIN, 2: SWIGLU's gate and up) against one x stream, U steps per batch.
-template <int F, int NW, int U>
+// NW weight streams (1: PLAIN, 2: SWIGLU's gate and up) against one x stream, U steps per batch. P: Params, or
+// BiasParams (NW == 1 only): wave 0 adds the output's bias to the summed accumulator, one fp32 add before the
+// one rounding; an output whose bias is NULL gets no add at all, so its bits are the plain form's.
+template <int F, int NW, int U, typename P = Params>
 __global__ __launch_bounds__(THREADS)
-void skinny_kernel(const Params p) {
+void skinny_kernel(const P p) {
     __shared__ f32x4 part[NW][WAVES][64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, h = lane >> 4;
@@ -115,6 +127,15 @@ void skinny_kernel(const Params p) {
         if (out) tile -= p.tile_end[out - 1];
     }
     const int n0 = tile * 16;
+    // the bias of this lane's four features, 8 bytes with the default cache policy: wave 0 alone asks for the
+    // workgroup's 16 features (32 bytes), first of all its loads, so the stream below hides the latency
+    const uint16_t* bp = nullptr;
+    uint2 bias = make_uint2(0u, 0u);
+    if constexpr (P::kBias) {
+        static_assert(NW == 1, "the bias epilogue is PLAIN's");
+        bp = p.b[out];
+        if (wave == 0 && bp) bias = *reinterpret_cast<const uint2*>(bp + n0 + 4 * h);
+    }
     const uint16_t* wp[NW];
     if constexpr (NW == 1) wp[0] = p.w[out] + (int64_t)(n0 + r) * p.ldw[out] + 8 * h;
     else {
@@ -174,6 +195,14 @@ void skinny_kernel(const Params p) {
         sum[i] = part[i][0][lane];
 #pragma unroll
         for (int w = 1; w < WAVES; ++w) sum[i] += part[i][w][lane];
+    }
+    if constexpr (P::kBias) {
+        if (bp) {                                           // uniform over the workgroup
+            sum[0][0] += u2f<F>(bias.x & 0xffffu);
+            sum[0][1] += u2f<F>(bias.x >> 16);
+            sum[0][2] += u2f<F>(bias.y & 0xffffu);
+            sum[0][3] += u2f<F>(bias.y >> 16);
+        }
     }
     uint32_t o[4];
 #pragma unroll
@@ -333,6 +362,45 @@ const char* check_sizes(int32_t M, int32_t K, const Out* outs, int32_t n_out, in
     return nullptr;
 }
 
+// The checks of smt_linear_skinny (sizes, null pointers and extents: -1; alignment: -2) and, if they pass, the
+// kernel's parameters and its grid. `fn` names the entry point in the message.
+int fill_params(const char* fn, const void* x, int64_t ldx, int32_t M, int32_t K, int32_t dtype, const SmtSkinnyOut* outs,
+                int32_t n_out, int32_t epilogue, Params& p, uint32_t& grid) {
+    if (const char* why = check_sizes<32>(M, K, outs, n_out, epilogue)) return fail(-1, "%s: %s", fn, why);
+    if (dtype != SMT_DTYPE_BF16 && dtype != SMT_DTYPE_FP16)
+        return fail(-1, "%s: dtype %d is not SMT_DTYPE_BF16 / _FP16", fn, (int)dtype);
+    const int n_y = epilogue == SMT_SKINNY_SWIGLU ? 1 : n_out;
+    if (!x) return fail(-1, "%s: null x", fn);
+    if (ldx < K) return fail(-1, "%s: ldx %lld < K %d", fn, (long long)ldx, (int)K);
+    for (int i = 0; i < n_out; ++i) {
+        if (!outs[i].w || (i < n_y && !outs[i].y)) return fail(-1, "%s: null w or y of output %d", fn, i);
+        if (outs[i].ldw < K || (i < n_y && outs[i].ldy < outs[i].N))
+            return fail(-1, "%s: ldw or ldy of output %d below its extent", fn, i);
+    }
+    if (!aligned16(x) || (ldx & 7)) return fail(-2, "%s: x must be 16-byte aligned, ldx %lld a multiple of 8", fn, (long long)ldx);
+    for (int i = 0; i < n_out; ++i) {
+        if (!aligned16(outs[i].w) || (outs[i].ldw & 7) || (i < n_y && (!aligned16(outs[i].y) || (outs[i].ldy & 7))))
+            return fail(-2, "%s: w, y of output %d must be 16-byte aligned, ldw, ldy multiples of 8", fn, i);
+    }
+    p.x = static_cast<const uint16_t*>(x);
+    p.ldx = ldx;
+    p.M = M;
+    p.K = K;
+    int32_t tiles = 0;
+    for (int i = 0; i < SMT_LINEAR_MAX_OUT; ++i) {
+        if (i < n_out) {
+            p.w[i] = static_cast<const uint16_t*>(outs[i].w);
+            p.ldw[i] = outs[i].ldw;
+            p.y[i] = static_cast<uint16_t*>(outs[i].y);
+            p.ldy[i] = outs[i].ldy;
+            tiles += outs[i].N / 16;
+        }
+        p.tile_end[i] = tiles;
+    }
+    grid = (uint32_t)(epilogue == SMT_SKINNY_SWIGLU ? outs[0].N / 16 : tiles);
+    return 0;
+}
+
 template <int F>
 int launch(const Params& p, int32_t epilogue, uint32_t grid, hipStream_t stream) {
     if (epilogue == SMT_SKINNY_SWIGLU)
@@ -369,41 +437,38 @@ int64_t smt_linear_skinny_workspace(int32_t M, int32_t K, const SmtSkinnyOut* ou
 int smt_linear_skinny(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t dtype, const SmtSkinnyOut* outs,
                       int32_t n_out, int32_t epilogue, void* workspace, hipStream_t stream) {
     (void)workspace;
-    if (const char* why = check_sizes<32>(M, K, outs, n_out, epilogue)) return fail(-1, "smt_linear_skinny: %s", why);
-    if (dtype != SMT_DTYPE_BF16 && dtype != SMT_DTYPE_FP16)
-        return fail(-1, "smt_linear_skinny: dtype %d is not SMT_DTYPE_BF16 / _FP16", (int)dtype);
-    const int n_y = epilogue == SMT_SKINNY_SWIGLU ? 1 : n_out;
-    if (!x) return fail(-1, "smt_linear_skinny: null x");
-    if (ldx < K) return fail(-1, "smt_linear_skinny: ldx %lld < K %d", (long long)ldx, (int)K);
-    for (int i = 0; i < n_out; ++i) {
-        if (!outs[i].w || (i < n_y && !outs[i].y)) return fail(-1, "smt_linear_skinny: null w or y of output %d", i);
-        if (outs[i].ldw < K || (i < n_y && outs[i].ldy < outs[i].N))
-            return fail(-1, "smt_linear_skinny: ldw or ldy of output %d below its extent", i);
-    }
-    if (!aligned16(x) || (ldx & 7)) return fail(-2, "smt_linear_skinny: x must be 16-byte aligned, ldx %lld a multiple of 8", (long long)ldx);
-    for (int i = 0; i < n_out; ++i) {
-        if (!aligned16(outs[i].w) || (outs[i].ldw & 7) || (i < n_y && (!aligned16(outs[i].y) || (outs[i].ldy & 7))))
-            return fail(-2, "smt_linear_skinny: w, y of output %d must be 16-byte aligned, ldw, ldy multiples of 8", i);
-    }
     Params p = {};
-    p.x = static_cast<const uint16_t*>(x);
-    p.ldx = ldx;
-    p.M = M;
-    p.K = K;
-    int32_t tiles = 0;
-    for (int i = 0; i < SMT_LINEAR_MAX_OUT; ++i) {
-        if (i < n_out) {
-            p.w[i] = static_cast<const uint16_t*>(outs[i].w);
-            p.ldw[i] = outs[i].ldw;
-            p.y[i] = static_cast<uint16_t*>(outs[i].y);
-            p.ldy[i] = outs[i].ldy;
-            tiles += outs[i].N / 16;
-        }
-        p.tile_end[i] = tiles;
-    }
-    const uint32_t grid = (uint32_t)(epilogue == SMT_SKINNY_SWIGLU ? outs[0].N / 16 : tiles);
+    uint32_t grid = 0;
+    if (const int rc = fill_params("smt_linear_skinny", x, ldx, M, K, dtype, outs, n_out, epilogue, p, grid)) return rc;
     if (dtype == SMT_DTYPE_BF16) return launch<SMT_DTYPE_BF16>(p, epilogue, grid, stream);
     return launch<SMT_DTYPE_FP16>(p, epilogue, grid, stream);
+}
+
+int smt_linear_skinny_bias(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t dtype, const SmtSkinnyOut* outs,
+                           const void* const* biases, int32_t n_out, int32_t epilogue, void* workspace,
+                           hipStream_t stream) {
+    (void)workspace;
+    BiasParams p = {};
+    uint32_t grid = 0;
+    if (const int rc = fill_params("smt_linear_skinny_bias", x, ldx, M, K, dtype, outs, n_out, epilogue, p, grid)) return rc;
+    if (!biases) return fail(-1, "smt_linear_skinny_bias: null biases (an array of n_out pointers, each of which may be null)");
+    bool any = false;
+    for (int i = 0; i < n_out; ++i) {
+        p.b[i] = static_cast<const uint16_t*>(biases[i]);
+        any = any || biases[i];
+    }
+    if (any && epilogue != SMT_SKINNY_PLAIN) return fail(-1, "smt_linear_skinny_bias: a bias goes with SMT_SKINNY_PLAIN only");
+    for (int i = 0; i < n_out; ++i)
+        if (!aligned16(biases[i])) return fail(-2, "smt_linear_skinny_bias: the bias of output %d must be 16-byte aligned", i);
+    if (!any) {                                              // nothing to add: the plain kernels
+        if (dtype == SMT_DTYPE_BF16) return launch<SMT_DTYPE_BF16>(p, epilogue, grid, stream);
+        return launch<SMT_DTYPE_FP16>(p, epilogue, grid, stream);
+    }
+    if (dtype == SMT_DTYPE_BF16) hipLaunchKernelGGL((skinny_kernel<SMT_DTYPE_BF16, 1, 8, BiasParams>), dim3(grid), dim3(THREADS), 0, stream, p);
+    else hipLaunchKernelGGL((skinny_kernel<SMT_DTYPE_FP16, 1, 8, BiasParams>), dim3(grid), dim3(THREADS), 0, stream, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(-4, "smt_linear_skinny_bias: %s", hipGetErrorString(e));
+    return 0;
 }
 
 int64_t smt_linear_skinny_fp8_workspace(int32_t M, int32_t K, const SmtSkinnyFp8Out* outs, int32_t n_out,

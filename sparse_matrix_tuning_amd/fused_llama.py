@@ -28,6 +28,12 @@ same stream on their e4m3 bytes (``smt_linear_skinny_fp8``; :func:`decode_linear
 :func:`decode_linear_group_fp8`, :func:`decode_swiglu_fp8`) at the sizes where it measured faster than
 ``quant_rows`` + ``torch._scaled_mm`` (tests/test_gpu_decode_linear_fp8.py, tests/test_gpu_generate_decode_fp8.py).
 
+:func:`patch_model` / :func:`unpatch_model` are :func:`patch_llama` / :func:`unpatch_llama` for any family of
+:data:`FAMILIES`, LLaMA and Qwen2 (the reference's other family, the DeepSeek-R1 distills): the family is read from
+the model's classes and the same body runs over its table entry. Qwen2's biased q, k and v go through the
+decode-linear kernel's bias epilogue (``smt_linear_skinny_bias``; tests/test_gpu_decode_linear_bias.py,
+tests/test_gpu_qwen2.py).
+
 The model's dtype is bf16 or, since ABI v13, fp16 (the reference's ``--dtype fp16``,
 ``fine_tune.py:955-959``): every kernel is one template body for both formats, rounding where the eager
 chain rounds to the model's dtype (tests/test_gpu_fused_fp16.py). fp32 models and mixed dtypes raise
@@ -482,7 +488,9 @@ def _grad_or_placeholder(like: torch.Tensor, grad, need) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 class DecodeLinearStats:
     """Routed launches of the decode-linear kernel by kind (``single``, ``group``: q/k/v in one launch,
-    ``swiglu``: gate, up and SwiGLU in one launch). A graph replay runs no Python and counts nothing."""
+    ``swiglu``: gate, up and SwiGLU in one launch). ``bias`` counts, among the ``single`` and ``group`` launches,
+    those that added at least one bias (smt_linear_skinny_bias), once per launch; it is an attribute beside
+    :meth:`as_dict`, whose keys stay the three kinds. A graph replay runs no Python and counts nothing."""
 
     def __init__(self):
         self.reset()
@@ -491,6 +499,7 @@ class DecodeLinearStats:
         self.single = 0
         self.group = 0
         self.swiglu = 0
+        self.bias = 0
 
     def as_dict(self) -> dict:
         return {"single": self.single, "group": self.group, "swiglu": self.swiglu}
@@ -501,6 +510,8 @@ decode_linear_stats = DecodeLinearStats()
 # each off): q/k/v as one grouped launch, and gate/up/SwiGLU as one launch
 DECODE_LINEAR_GROUP = True
 DECODE_LINEAR_SWIGLU = True
+# biased projections (Qwen2's q, k and v) go to the kernel's bias epilogue; off: they run what they ran before
+DECODE_LINEAR_BIAS = True
 # The routing's size rule: a launch goes to the kernel only if K <= 4096 and its weights hold at most 2^25
 # elements (sum of N times K; 64 MiB of 16-bit weights). Every measured launch inside the rule, (N, K) =
 # (4096, 4096), (1024, 4096) and the grouped (6144, 4096), is 1.3-3.0x faster than hipBLASLt, which sits on a
@@ -509,29 +520,48 @@ DECODE_LINEAR_SWIGLU = True
 # (profiles/r20_decode_linear_bench.jsonl).
 DECODE_LINEAR_MAX_K = 4096
 DECODE_LINEAR_MAX_WEIGHT_ELEMS = 1 << 25
+# Biased launches (against F.linear(x, W, b) per projection, profiles/r22_decode_linear_bench.jsonl): the grouped
+# q/k/v launches, 2048 x 1536 and 4608 x 3584, are 2.0-6.9x faster at M = 1, 4, 16 and every single launch at
+# K = 1536 is 1.19-2.2x faster, so those stay inside the rule above. A single biased weight at K = 3584 is faster
+# at M <= 4 (1.08-2.0x) but at M = 16 3584 x 3584 gains only 1.03x and 512 x 3584 loses (0.91-0.93x): a single
+# biased launch with K above DECODE_LINEAR_BIAS_SINGLE_MAX_K is routed at up to DECODE_LINEAR_BIAS_FEW_ROWS rows
+# only (rows 5-15 were not timed and count as 16).
+DECODE_LINEAR_BIAS_SINGLE_MAX_K = 2048
+DECODE_LINEAR_BIAS_FEW_ROWS = 4
 
 
-def _decode_routes(x, weights, biases=(), need_cuda: bool = True) -> bool:
-    """The routing's decision for one launch: :func:`decode_linear_reason` admits it and the size rule holds."""
-    return (decode_linear_reason(x, weights, biases, need_cuda) is None
-            and x.shape[-1] <= DECODE_LINEAR_MAX_K
-            and sum(w.shape[0] for w in weights) * x.shape[-1] <= DECODE_LINEAR_MAX_WEIGHT_ELEMS)
+def _decode_routes(x, weights, biases=(), need_cuda: bool = True, allow_bias: bool = False) -> bool:
+    """The routing's decision for one launch: :func:`decode_linear_reason` admits it and the size rule holds,
+    for a single biased weight also the ``DECODE_LINEAR_BIAS_*`` constants. ``allow_bias``: only the PLAIN call
+    sites of :func:`decode_routed_linear_forward` pass it; the gate/up/SwiGLU launch has no biased form, so a
+    biased MLP pair is refused here and runs the unfused path."""
+    if decode_linear_reason(x, weights, biases, need_cuda, allow_bias=allow_bias) is not None:
+        return False
+    K = x.shape[-1]
+    if (len(weights) == 1 and any(b is not None for b in biases) and K > DECODE_LINEAR_BIAS_SINGLE_MAX_K
+            and x.numel() // K > DECODE_LINEAR_BIAS_FEW_ROWS):
+        return False
+    return K <= DECODE_LINEAR_MAX_K and sum(w.shape[0] for w in weights) * K <= DECODE_LINEAR_MAX_WEIGHT_ELEMS
 
 
 def _aligned16(t: torch.Tensor) -> bool:
     return (t.storage_offset() * t.element_size()) % 16 == 0 and (t.device.type == "meta" or t.data_ptr() % 16 == 0)
 
 
-def decode_linear_reason(x: torch.Tensor, weights, biases=(), need_cuda: bool = True):
+def decode_linear_reason(x: torch.Tensor, weights, biases=(), need_cuda: bool = True, allow_bias: bool = False):
     """Why ``x @ W^T`` for these weights cannot go to the decode-linear kernel (smt_linear_skinny), or
     None if it can. The one predicate of the routing; every condition of include/smt_linear.h:
     gradients off; ROCm bf16 / fp16 tensors of one dtype; 1..16 rows after flattening the leading
     dimensions; no bias and no fp8 copy on a weight; K % 32 == 0, N % 16 == 0; unit inner strides, row
     strides multiples of 8 and 16-byte aligned storage. ``need_cuda=False`` lifts the device condition
-    (the host tests run the rest on CPU and meta tensors)."""
+    (the host tests run the rest on CPU and meta tensors). ``allow_bias=True`` (the routing's form) admits
+    biases that the bias epilogue takes (smt_linear_skinny_bias): one entry per weight, each None or 1-D ``[N]``
+    of x's dtype on x's device, unit stride, 16-byte aligned, no gradient needed."""
     if torch.is_grad_enabled():
+        if allow_bias and any(b is not None and b.requires_grad for b in biases):
+            return "bias needs a gradient (gradients are enabled)"
         return "gradients are enabled"
-    if any(b is not None for b in biases):
+    if not allow_bias and any(b is not None for b in biases):
         return "bias"
     if x.dtype not in (torch.bfloat16, torch.float16):
         return f"dtype {x.dtype}"
@@ -562,36 +592,54 @@ def decode_linear_reason(x: torch.Tensor, weights, biases=(), need_cuda: bool = 
             return f"N {w.shape[0]} is not a multiple of 16"
         if w.stride(1) != 1 or w.stride(0) % 8 or w.stride(0) < K or not _aligned16(w):
             return "weight stride or alignment"
+    if any(b is not None for b in biases):
+        if len(biases) != len(weights):
+            return f"{len(biases)} biases for {len(weights)} weights"
+        for b, w in zip(biases, weights):
+            if b is None:
+                continue
+            if b.dim() != 1 or b.shape[0] != w.shape[0]:
+                return f"bias shape {tuple(b.shape)} for N {w.shape[0]}"
+            if b.dtype != x.dtype or b.device != x.device:
+                return f"bias {b.dtype} on {b.device} beside x {x.dtype} on {x.device}"
+            if b.stride(0) != 1 or not _aligned16(b):
+                return "bias stride or alignment"
     return None
 
 
-def _decode_call(x, weights, epilogue, what):
-    why = decode_linear_reason(x, weights)
+def _decode_call(x, weights, epilogue, what, biases=None):
+    biased = biases is not None and any(b is not None for b in biases)
+    why = decode_linear_reason(x, weights, tuple(biases) if biased else (), allow_bias=True)
     if why is not None:                 # no quiet fall-back: the routing asks the predicate first
         raise RuntimeError(f"{what}: the call does not qualify for the decode-linear kernel ({why})")
     if epilogue == _hip.SKINNY_SWIGLU and weights[0].shape[0] != weights[1].shape[0]:
         raise RuntimeError(f"{what}: gate and up of unequal width")
     K = x.shape[-1]
-    ys = _hip.linear_skinny(x.reshape(-1, K), list(weights), epilogue)
+    ys = _hip.linear_skinny(x.reshape(-1, K), list(weights), epilogue, biases=list(biases) if biased else None)
+    if biased:
+        decode_linear_stats.bias += 1
     return [y.view(*x.shape[:-1], y.shape[-1]) for y in ys]
 
 
-def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
-    """``x @ weight^T`` for at most 16 rows of ``x``: the weight-streaming kernel on a ROCm device (an
-    error if the call does not qualify, :func:`decode_linear_reason`), torch's matmul on the CPU."""
+def decode_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor = None) -> torch.Tensor:
+    """``x @ weight^T (+ bias)`` for at most 16 rows of ``x``: the weight-streaming kernel on a ROCm device (an
+    error if the call does not qualify, :func:`decode_linear_reason`), ``F.linear`` on the CPU. The bias is
+    added in fp32 before the one rounding (smt_linear_skinny_bias)."""
     if x.device.type != "cuda":
-        return torch.matmul(x, weight.t())
-    y = _decode_call(x, (weight,), _hip.SKINNY_PLAIN, "decode_linear")[0]
+        return torch.matmul(x, weight.t()) if bias is None else torch.nn.functional.linear(x, weight, bias)
+    y = _decode_call(x, (weight,), _hip.SKINNY_PLAIN, "decode_linear", None if bias is None else (bias,))[0]
     decode_linear_stats.single += 1
     return y
 
 
-def decode_linear_group(x: torch.Tensor, weights) -> list:
+def decode_linear_group(x: torch.Tensor, weights, biases=None) -> list:
     """``[x @ W^T for W in weights]`` (1..3 weights) as one launch that reads ``x`` once; bit for bit
-    the single calls."""
+    the single calls. ``biases``: one entry per weight, None or that output's bias."""
     if x.device.type != "cuda":
-        return [torch.matmul(x, w.t()) for w in weights]
-    ys = _decode_call(x, tuple(weights), _hip.SKINNY_PLAIN, "decode_linear_group")
+        if biases is None:
+            return [torch.matmul(x, w.t()) for w in weights]
+        return [torch.matmul(x, w.t()) if b is None else torch.nn.functional.linear(x, w, b) for w, b in zip(weights, biases)]
+    ys = _decode_call(x, tuple(weights), _hip.SKINNY_PLAIN, "decode_linear_group", biases)
     decode_linear_stats.group += 1
     return ys
 
@@ -784,6 +832,8 @@ def decode_routed_linear_forward(self, x):
         else:
             del x.__dict__["_smt_decode_kv"]
     bias = getattr(self, "bias", None)
+    # the bias epilogue: on for what patch_model / route_decode_linears(bias=True) routed, while the switch is on
+    with_bias = bool(DECODE_LINEAR_BIAS and self.__dict__.get("_smt_decode_bias"))
     fp8 = self.__dict__.get("_smt_decode_fp8", False)
     group = self.__dict__.get("_smt_decode_group")
     if group is not None and DECODE_LINEAR_GROUP:
@@ -795,17 +845,18 @@ def decode_routed_linear_forward(self, x):
                 q, k, v = decode_linear_group_fp8(x, ws)
                 x.__dict__["_smt_decode_kv"] = [x._version, ws[1], k, ws[2], v]
                 return q
-            if _decode_routes(x, ws, (bias, kv[0].bias, kv[1].bias)):
+            bs = (bias, kv[0].bias, kv[1].bias)
+            if _decode_routes(x, ws, bs, allow_bias=with_bias):
                 _sync_for_decode(self, *kv)
-                q, k, v = decode_linear_group(x, ws)
+                q, k, v = decode_linear_group(x, ws, bs)
                 x.__dict__["_smt_decode_kv"] = [x._version, ws[1], k, ws[2], v]
                 return q
     if fp8 and _decode_fp8_routes(x, (self.weight,), (bias,)):
         _sync_for_decode(self)
         return decode_linear_fp8(x, self.weight)
-    if _decode_routes(x, (self.weight,), (bias,)):
+    if _decode_routes(x, (self.weight,), (bias,), allow_bias=with_bias):
         _sync_for_decode(self)
-        return decode_linear(x, self.weight)
+        return decode_linear(x, self.weight, bias)
     return _decode_prev_forward(self, x)
 
 
@@ -829,25 +880,31 @@ def _unroute_decode_linear(m) -> None:
             m.__dict__["forward"] = prev
     m.__dict__.pop("_smt_decode_group", None)
     m.__dict__.pop("_smt_decode_fp8", None)
+    m.__dict__.pop("_smt_decode_bias", None)
 
 
-def route_decode_linears(model: nn.Module, fp8: bool = False) -> int:
+def route_decode_linears(model: nn.Module, fp8: bool = False, family: "ModelFamily" = None, bias: bool = True) -> int:
     """What ``patch_llama(decode_linears=True)`` adds, by itself: the routed forwards of the projections
     and of a bias-free ``lm_head``, the q/k/v group and the MLPs' fused launch. ``fp8``
     (``patch_llama(decode_fp8=True)``): the routed forwards and the MLPs first try the e4m3 kernel on weights
-    that carry an fp8 copy. Returns the number of linears
+    that carry an fp8 copy. ``family``: whose classes to match. The default is now the model's own
+    (:func:`model_family`), else LLaMA's: a direct call on a Qwen2 model, which used to match no class and route
+    nothing, routes its projections. ``bias`` (default on): the routed projections that carry a bias go to the
+    kernel's bias epilogue; off, they run what they ran before, as every biased projection did until now.
+    :func:`patch_llama` passes the LLaMA family and ``bias=False`` and so routes exactly what it always routed;
+    :func:`patch_model` passes the model's family and ``bias=True``. Returns the number of linears
     routed by this call. :func:`unroute_decode_linears` (and :func:`unpatch_llama`) removes all of it."""
-    ml = _ml()
+    fam = family or model_family(model) or FAMILIES["llama"]
     routed = 0
     for m in model.modules():
-        if isinstance(m, ml.LlamaAttention):
+        if isinstance(m, fam.attention):
             names = ("q_proj", "k_proj", "v_proj", "o_proj")
-        elif isinstance(m, ml.LlamaMLP):
+        elif isinstance(m, fam.mlp):
             names = ("gate_proj", "up_proj", "down_proj")
             m.__dict__["_smt_decode_linears"] = True
             if fp8:
                 m.__dict__["_smt_decode_fp8"] = True
-        elif isinstance(m, ml.LlamaForCausalLM):
+        elif isinstance(m, fam.causal_lm):
             names = ("lm_head",) if getattr(getattr(m, "lm_head", None), "bias", None) is None else ()
         else:
             continue
@@ -858,7 +915,9 @@ def route_decode_linears(model: nn.Module, fp8: bool = False) -> int:
                 routed += 1
             if fp8 and lin is not None and lin.__dict__.get("_smt_decode_routed"):
                 lin.__dict__["_smt_decode_fp8"] = True
-        if isinstance(m, ml.LlamaAttention) and all(
+            if bias and lin is not None and lin.__dict__.get("_smt_decode_routed"):
+                lin.__dict__["_smt_decode_bias"] = True
+        if isinstance(m, fam.attention) and all(
                 getattr(m, n, None) is not None and getattr(m, n).__dict__.get("_smt_decode_routed") for n in names[:3]):
             m.q_proj.__dict__["_smt_decode_group"] = (weakref.ref(m.k_proj), weakref.ref(m.v_proj))
     return routed
@@ -1892,11 +1951,58 @@ def register_attention() -> str:
 _EAGER = {}
 
 
+class ModelFamily:
+    """One architecture the fused path serves: its transformers modelling module (imported on first use), whose
+    module-level ``apply_rotary_pos_emb`` the attention looks up at call time, and the classes the patch
+    matches. ``rope_key``: where ``_EAGER`` keeps transformers' own function while the module global is patched."""
+
+    def __init__(self, name, module, rmsnorm, mlp, decoder, attention, causal_lm, rope_key):
+        self.name, self.module_name, self.rope_key = name, module, rope_key
+        self._names = dict(rmsnorm=rmsnorm, mlp=mlp, decoder=decoder, attention=attention, causal_lm=causal_lm)
+
+    @property
+    def module(self):
+        import importlib
+        ml = importlib.import_module(self.module_name)
+        if self.rope_key not in _EAGER:
+            _EAGER[self.rope_key] = ml.apply_rotary_pos_emb
+        return ml
+
+    def __getattr__(self, kind):
+        names = self.__dict__.get("_names", {})
+        if kind not in names:
+            raise AttributeError(kind)
+        return getattr(self.module, names[kind])
+
+
+FAMILIES = {
+    "llama": ModelFamily("llama", "transformers.models.llama.modeling_llama", "LlamaRMSNorm", "LlamaMLP",
+                         "LlamaDecoderLayer", "LlamaAttention", "LlamaForCausalLM", "rope"),
+    "qwen2": ModelFamily("qwen2", "transformers.models.qwen2.modeling_qwen2", "Qwen2RMSNorm", "Qwen2MLP",
+                         "Qwen2DecoderLayer", "Qwen2Attention", "Qwen2ForCausalLM", "rope_qwen2"),
+}
+_KINDS = ("rmsnorm", "mlp", "decoder", "attention", "causal_lm")
+
+
+def model_family(model: nn.Module):
+    """The :data:`FAMILIES` entry whose classes ``model`` is built from, or None. A family whose modelling module
+    was never imported cannot have built the model and is not imported for the question."""
+    for fam in FAMILIES.values():
+        if _has_classes_of(model, fam):
+            return fam
+    return None
+
+
+def _has_classes_of(model: nn.Module, fam) -> bool:
+    import sys
+    if fam.module_name not in sys.modules:
+        return False
+    classes = tuple(getattr(fam, k) for k in _KINDS)
+    return any(isinstance(m, classes) for m in model.modules())
+
+
 def _ml():
-    from transformers.models.llama import modeling_llama as ml
-    if "rope" not in _EAGER:
-        _EAGER["rope"] = ml.apply_rotary_pos_emb
-    return ml
+    return FAMILIES["llama"].module
 
 
 def eager_apply_rotary_pos_emb(*a, **k):
@@ -2038,6 +2144,68 @@ def _keep_2d_mask(config=None, inputs_embeds=None, attention_mask=None, **kwargs
     return attention_mask
 
 
+def _patch(model, fam, what, attention, loss, lm_head_loss, decode_linears, decode_fp8) -> dict:
+    """The body of :func:`patch_llama` and :func:`patch_model` over the classes of ``fam``."""
+    if decode_fp8 and not decode_linears:
+        raise ValueError(f"{what}(decode_fp8=True) needs decode_linears=True: the fp8 route is part of that routing")
+    ml = fam.module
+    counts = {"rmsnorm": 0, "mlp": 0, "rope": 1, "attention": 0, "loss": 0, "decoder": 0, "lm_head_loss": 0}
+    if lm_head_loss is None:
+        lm_head_loss = os.environ.get("SMT_LM_HEAD_LOSS", "1") != "0"
+    if loss and hasattr(type(model), "loss_function"):
+        model.loss_function = fused_causal_lm_loss
+        counts["loss"] = 1
+        if lm_head_loss and isinstance(model, fam.causal_lm):
+            model.forward = fused_causal_lm_forward.__get__(model, type(model))
+            counts["lm_head_loss"] = 1
+    if attention:
+        cfg = getattr(model, "config", None)
+        if cfg is None:
+            raise RuntimeError(f"{what}(attention=True) needs a transformers model with a config")
+        if "smt_prev_attn" not in _EAGER:
+            _EAGER["smt_prev_attn"] = cfg._attn_implementation
+        cfg._attn_implementation = register_attention()
+        counts["attention"] = sum(1 for m in model.modules() if isinstance(m, fam.attention))
+        # generate() sends a static cache on a GPU through torch.compile unless told otherwise, and
+        # torch.compile cannot trace the ctypes launches
+        gen = getattr(model, "generation_config", None)
+        if gen is not None and "_smt_prev_disable_compile" not in model.__dict__:
+            model.__dict__["_smt_prev_disable_compile"] = getattr(gen, "disable_compile", False)
+            gen.disable_compile = True
+        if isinstance(model, fam.causal_lm):
+            # the model-level forward that hands the decode steps of a BeamSharedCache(graph=True) to the
+            # cache's DecodeGraph; every other call passes through to what ran before
+            model.__dict__["_smt_lm_head_forward"] = bool(counts["lm_head_loss"])
+            model.forward = smt_causal_lm_forward.__get__(model, type(model))
+        if gen is not None:
+            # ... and, for a compilable cache, builds the mask before the forward and passes the
+            # result in place of the 2-D mask; only a 4-D tensor survives that. Keep the 2-D mask:
+            # the forward builds the CacheMask itself, as with a DynamicCache.
+            model.__dict__["create_masks_for_generate"] = _keep_2d_mask
+    for m in model.modules():
+        if isinstance(m, fam.rmsnorm):
+            m.forward = fused_rmsnorm_forward.__get__(m, type(m))
+            counts["rmsnorm"] += 1
+        elif isinstance(m, fam.decoder):
+            m.forward = fused_decoder_layer_forward.__get__(m, type(m))
+            counts["decoder"] += 1
+        elif isinstance(m, fam.mlp):
+            act = getattr(m, "act_fn", None)
+            if act is None or "silu" not in type(act).__name__.lower():
+                raise NotImplementedError(f"fused MLP: SiLU activation only (got {type(act).__name__})")
+            m.forward = fused_mlp_forward.__get__(m, type(m))
+            counts["mlp"] += 1
+        elif isinstance(m, nn.ModuleList) and len(m) > 1 and all(isinstance(x, fam.decoder) for x in m):
+            # each decoder layer's fused tail normalises for the layer after it (a weak reference:
+            # not a submodule)
+            for i in range(len(m) - 1):
+                m[i].__dict__["_smt_next_layer"] = weakref.ref(m[i + 1])
+    ml.apply_rotary_pos_emb = fused_apply_rotary_pos_emb
+    if decode_linears:
+        counts["decode_linears"] = route_decode_linears(model, fp8=decode_fp8, family=fam, bias=what == "patch_model")
+    return counts
+
+
 def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_head_loss: bool = None,
                 decode_linears: bool = False, decode_fp8: bool = False) -> dict:
     """Route a transformers LLaMA model's RMSNorm / RoPE / SwiGLU / attention-residual add (and, with ``attention``, its
@@ -2066,70 +2234,17 @@ def patch_llama(model: nn.Module, attention: bool = True, loss: bool = True, lm_
     kernel (smt_linear_skinny_fp8) where :func:`decode_linear_fp8_reason` admits the call and the
     ``DECODE_FP8_*`` size rule holds, and then fall through to what they do without it.
     Returns counts of patched modules (with ``decode_linears``, also the routed linears). Idempotent."""
-    if decode_fp8 and not decode_linears:
-        raise ValueError("patch_llama(decode_fp8=True) needs decode_linears=True: the fp8 route is part of that routing")
-    ml = _ml()
-    counts = {"rmsnorm": 0, "mlp": 0, "rope": 1, "attention": 0, "loss": 0, "decoder": 0, "lm_head_loss": 0}
-    if lm_head_loss is None:
-        lm_head_loss = os.environ.get("SMT_LM_HEAD_LOSS", "1") != "0"
-    if loss and hasattr(type(model), "loss_function"):
-        model.loss_function = fused_causal_lm_loss
-        counts["loss"] = 1
-        if lm_head_loss and isinstance(model, ml.LlamaForCausalLM):
-            model.forward = fused_causal_lm_forward.__get__(model, type(model))
-            counts["lm_head_loss"] = 1
-    if attention:
-        cfg = getattr(model, "config", None)
-        if cfg is None:
-            raise RuntimeError("patch_llama(attention=True) needs a transformers model with a config")
-        if "smt_prev_attn" not in _EAGER:
-            _EAGER["smt_prev_attn"] = cfg._attn_implementation
-        cfg._attn_implementation = register_attention()
-        counts["attention"] = sum(1 for m in model.modules() if isinstance(m, ml.LlamaAttention))
-        # generate() sends a static cache on a GPU through torch.compile unless told otherwise, and
-        # torch.compile cannot trace the ctypes launches
-        gen = getattr(model, "generation_config", None)
-        if gen is not None and "_smt_prev_disable_compile" not in model.__dict__:
-            model.__dict__["_smt_prev_disable_compile"] = getattr(gen, "disable_compile", False)
-            gen.disable_compile = True
-        if isinstance(model, ml.LlamaForCausalLM):
-            # the model-level forward that hands the decode steps of a BeamSharedCache(graph=True) to the
-            # cache's DecodeGraph; every other call passes through to what ran before
-            model.__dict__["_smt_lm_head_forward"] = bool(counts["lm_head_loss"])
-            model.forward = smt_causal_lm_forward.__get__(model, type(model))
-        if gen is not None:
-            # ... and, for a compilable cache, builds the mask before the forward and passes the
-            # result in place of the 2-D mask; only a 4-D tensor survives that. Keep the 2-D mask:
-            # the forward builds the CacheMask itself, as with a DynamicCache.
-            model.__dict__["create_masks_for_generate"] = _keep_2d_mask
-    for m in model.modules():
-        if isinstance(m, ml.LlamaRMSNorm):
-            m.forward = fused_rmsnorm_forward.__get__(m, type(m))
-            counts["rmsnorm"] += 1
-        elif isinstance(m, ml.LlamaDecoderLayer):
-            m.forward = fused_decoder_layer_forward.__get__(m, type(m))
-            counts["decoder"] += 1
-        elif isinstance(m, ml.LlamaMLP):
-            act = getattr(m, "act_fn", None)
-            if act is None or "silu" not in type(act).__name__.lower():
-                raise NotImplementedError(f"fused MLP: SiLU activation only (got {type(act).__name__})")
-            m.forward = fused_mlp_forward.__get__(m, type(m))
-            counts["mlp"] += 1
-        elif isinstance(m, nn.ModuleList) and len(m) > 1 and all(isinstance(x, ml.LlamaDecoderLayer) for x in m):
-            # each decoder layer's fused tail normalises for the layer after it (a weak reference:
-            # not a submodule)
-            for i in range(len(m) - 1):
-                m[i].__dict__["_smt_next_layer"] = weakref.ref(m[i + 1])
-    ml.apply_rotary_pos_emb = fused_apply_rotary_pos_emb
-    if decode_linears:
-        counts["decode_linears"] = route_decode_linears(model, fp8=decode_fp8)
-    return counts
+    return _patch(model, FAMILIES["llama"], "patch_llama", attention, loss, lm_head_loss, decode_linears, decode_fp8)
 
 
 def unpatch_llama(model: nn.Module = None) -> None:
     """Undo :func:`patch_llama` (module-level RoPE; per-instance forwards of ``model`` if given)."""
-    ml = _ml()
-    ml.apply_rotary_pos_emb = _EAGER["rope"]
+    _unpatch(model, FAMILIES["llama"])
+
+
+def _unpatch(model, fam) -> None:
+    ml = fam.module
+    ml.apply_rotary_pos_emb = _EAGER[fam.rope_key]
     if model is not None and "smt_prev_attn" in _EAGER and getattr(model, "config", None) is not None:
         model.config._attn_implementation = _EAGER.pop("smt_prev_attn")
     if model is not None:
@@ -2145,7 +2260,61 @@ def unpatch_llama(model: nn.Module = None) -> None:
             del model.__dict__["forward"]
         model.__dict__.pop("_smt_lm_head_forward", None)
         for m in model.modules():
-            if isinstance(m, (ml.LlamaRMSNorm, ml.LlamaMLP, ml.LlamaDecoderLayer)) and "forward" in m.__dict__:
+            if isinstance(m, (fam.rmsnorm, fam.mlp, fam.decoder)) and "forward" in m.__dict__:
                 del m.__dict__["forward"]
             m.__dict__.pop("_smt_next_layer", None)
         unroute_decode_linears(model)
+
+
+def _refusal(model: nn.Module, fam) -> str:
+    """Why :func:`patch_model` cannot serve ``model``, or None. Asked before anything is changed."""
+    if fam is None:
+        return (f"{type(model).__name__} is of no family the fused path knows "
+                f"({', '.join(sorted(FAMILIES))}: their transformers classes)")
+    others = [f for f in FAMILIES.values() if f is not fam and _has_classes_of(model, f)]
+    if others:
+        return f"the model mixes the classes of {fam.name} and {others[0].name}"
+    cfg = getattr(model, "config", None)
+    if cfg is None:
+        return "the model has no transformers config"
+    layer_types = getattr(cfg, "layer_types", None) or ()
+    if "sliding_attention" in layer_types:
+        return ("layer_types holds 'sliding_attention': the smt_flash kernels have no sliding window "
+                f"({sum(1 for t in layer_types if t == 'sliding_attention')} of {len(layer_types)} layers)")
+    head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+    if head_dim != 128:
+        return f"head_dim {head_dim}: the attention kernels are built for 128"
+    for m in model.modules():
+        if isinstance(m, fam.mlp):
+            act = getattr(m, "act_fn", None)
+            if act is None or "silu" not in type(act).__name__.lower():
+                return f"fused MLP: SiLU activation only (got {type(act).__name__})"
+    return None
+
+
+def patch_model(model: nn.Module, attention: bool = True, loss: bool = True, lm_head_loss: bool = None,
+                decode_linears: bool = False, decode_fp8: bool = False) -> dict:
+    """:func:`patch_llama` for any family of :data:`FAMILIES` (LLaMA, Qwen2): the family is read from the
+    model's classes and the same body runs over that family's RMSNorm, MLP, decoder-layer, attention and
+    causal-LM classes and its modelling module's ``apply_rotary_pos_emb``; the keywords and the returned counts
+    are :func:`patch_llama`'s. One thing differs from :func:`patch_llama` on a LLaMA model as well: with
+    ``decode_linears`` the routed projections that carry a bias (Qwen2's q, k and v; a LLaMA model's with
+    ``attention_bias=True``) go through the decode-linear kernel's bias epilogue, where :func:`patch_llama` leaves
+    them on ``F.linear`` as before. The fused gate/up/SwiGLU launch takes no bias under either.
+    Refused with ``NotImplementedError`` before anything is changed: a model of no known family or of two, a
+    config whose ``layer_types`` holds ``"sliding_attention"``, a ``head_dim`` other than 128, an MLP whose
+    activation is not SiLU. The RoPE patch is process-global per family, as :func:`patch_llama`'s is."""
+    fam = model_family(model)
+    why = _refusal(model, fam)
+    if why is not None:
+        raise NotImplementedError(f"patch_model: {why}")
+    return _patch(model, fam, "patch_model", attention, loss, lm_head_loss, decode_linears, decode_fp8)
+
+
+def unpatch_model(model: nn.Module) -> None:
+    """Undo :func:`patch_model`: the per-instance forwards of ``model`` and the module-level RoPE of the
+    model's family; the other family's modelling module is left as it is."""
+    fam = model_family(model)
+    if fam is None:
+        raise NotImplementedError(f"unpatch_model: {type(model).__name__} is of no family the fused path knows")
+    _unpatch(model, fam)
