@@ -41,7 +41,13 @@ with ``engine.attach_fp8_weights`` (config 5): ``fp8_base`` = that model as ``pa
 (``fp8.quant_rows`` + ``torch._scaled_mm`` per projection: the baseline of the other two), ``fp8`` = with
 ``patch_llama(decode_linears=True, decode_fp8=True)``'s routing and its ``DECODE_FP8_*`` size rule, and
 ``fp8_unbounded`` = the same with the rule removed (every qualifying launch on the e4m3 kernel). Their lines carry
-``fp8_launches`` (``decode_fp8_stats``) and the ratio line ``seconds_fp8_base_over_<variant>`` per loop."""
+``fp8_launches`` (``decode_fp8_stats``) and the ratio line ``seconds_fp8_base_over_<variant>`` per loop.
+
+``--sample`` decodes with ``do_sample=True, temperature=0.6, top_k=50, top_p=0.95`` (run it with ``--beams 1`` and the
+rows as ``--prompts``), and ``--loop transformers smt_sample`` puts ``custom_generate=smt_sample``
+(sparse_matrix_tuning_amd/sampling.py: the selection of a token as one smt_sample_token call) beside transformers'
+``_sample``. The two draw from different streams, so their tokens differ; the ratio line carries
+``seconds_<leg>_transformers_over_smt_sample`` for every leg that ran under both."""
 import argparse
 import json
 import os
@@ -52,7 +58,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import MODELS, build_model  # noqa: E402
-from sparse_matrix_tuning_amd import beam_search  # noqa: E402
+from sparse_matrix_tuning_amd import beam_search, sampling  # noqa: E402
 from sparse_matrix_tuning_amd.beam_cache import BeamSharedCache  # noqa: E402
 from sparse_matrix_tuning_amd import fused_llama  # noqa: E402
 from sparse_matrix_tuning_amd.fused_llama import DecodeGraph, patch_model  # noqa: E402
@@ -98,7 +104,8 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=256)
     ap.add_argument("--new", type=int, nargs="+", default=[64])
     ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--loop", nargs="+", default=["transformers"], choices=["transformers", "smt"])
+    ap.add_argument("--loop", nargs="+", default=["transformers"], choices=["transformers", "smt", "smt_sample"])
+    ap.add_argument("--sample", action="store_true", help="do_sample=True, temperature 0.6, top_k 50, top_p 0.95")
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--caches", nargs="+", default=["dynamic", "static", "beam_shared", "beam_shared_graph"],
                     choices=["dynamic", "static", "beam_shared", "beam_shared_graph"])
@@ -153,7 +160,9 @@ def main():
                   "beam_shared": lambda: {"past_key_values": BeamSharedCache(model.config, a.beams, new)},
                   "beam_shared_graph": lambda: {"past_key_values": BeamSharedCache(model.config, a.beams, new, graph=True)}}
         extra = {} if a.repetition_penalty == 1.0 else {"repetition_penalty": a.repetition_penalty}
-        loops = {"transformers": {}, "smt": {"custom_generate": beam_search.smt_beam_search}}
+        loops = {"transformers": {}, "smt": {"custom_generate": beam_search.smt_beam_search},
+                 "smt_sample": {"custom_generate": sampling.smt_sample, "sample_seed": 1}}
+        mode = dict(do_sample=True, temperature=0.6, top_k=50, top_p=0.95) if a.sample else dict(do_sample=False)
         leg = lambda cache, loop: cache if loop == "transformers" else f"{cache}+{loop}"
         variants = lambda c: [None] + ((list(a.decode_linears or ()) + (list(FP8_VARIANTS) if a.fp8 else []))
                                        if c == "beam_shared_graph" else [])
@@ -190,12 +199,13 @@ def main():
             fused_llama.decode_linear_stats.reset()
             fused_llama.decode_fp8_stats.reset()
             beam_search.stats.reset()
+            sampling.stats.reset()
             m = fp8_model if v in FP8_VARIANTS else model
             torch.cuda.synchronize()
             t = time.perf_counter()
             with torch.no_grad():
-                out = m.generate(input_ids=ids, attention_mask=mask, num_beams=a.beams, do_sample=False,
-                                     max_new_tokens=new, min_new_tokens=new, **kw)
+                out = m.generate(input_ids=ids, attention_mask=mask, num_beams=a.beams, max_new_tokens=new,
+                                 min_new_tokens=new, **mode, **kw)
             torch.cuda.synchronize()
             return time.perf_counter() - t, out, kw.get("past_key_values")
 
@@ -208,7 +218,7 @@ def main():
             for name, kw in kinds:
                 s, out, cache = run(kw, variant_of(name))
                 secs[name] = s
-                line = {"cache": name.split("+")[0].split("@")[0], "loop": "smt" if name.endswith("+smt") else "transformers",
+                line = {"cache": name.split("+")[0].split("@")[0], "loop": name.partition("+")[2] or "transformers",
                         "repetition_penalty": a.repetition_penalty,
                         "round": rnd, "model": a.model, "prompts": a.prompts, "beams": a.beams,
                         "prompt_len": a.prompt_len, "new_tokens": new, "seconds": round(s, 4),
@@ -222,8 +232,8 @@ def main():
                     base = name.replace("@" + str(variant_of(name)), "@fp8_base" if variant_of(name) in FP8_VARIANTS else "")
                     if variant_of(name) is not None and base in outs:
                         line.update(same_tokens_as_unrouted=bool(torch.equal(outs[base], outs[name])))
-                if name.endswith("+smt"):
-                    line.update(delegated=beam_search.stats.delegated)
+                if "+" in name:
+                    line.update(delegated=(sampling if name.endswith("+smt_sample") else beam_search).stats.delegated)
                     if name.split("+")[0] in outs:
                         line.update(same_tokens_as_transformers_loop=bool(torch.equal(outs[name.split("+")[0]], outs[name])))
                 if name.startswith("beam_shared_graph"):
@@ -249,6 +259,9 @@ def main():
             for c in a.caches:
                 if c in secs and c + "+smt" in secs:
                     ratio[f"seconds_{c}_transformers_over_smt"] = round(secs[c] / secs[c + "+smt"], 3)
+            for name in secs:
+                if name + "+smt_sample" in secs:
+                    ratio[f"seconds_{name}_transformers_over_smt_sample"] = round(secs[name] / secs[name + "+smt_sample"], 3)
             print(json.dumps(ratio), flush=True)
 
 

@@ -28,7 +28,7 @@ ABI_VERSION = 13            # include/smt_hip.h: 16-bit dtype of the model ops /
                             # smt_adamw_args.param_dtype (v12), smt_wgrad_module.operand_dtype (v11)
 
 # Every function the headers declare (include/smt_hip.h, smt_model_ops.h, smt_attention.h, smt_fp8.h, smt_beam.h,
-# smt_linear.h); tests check the
+# smt_linear.h, smt_sample.h); tests check the
 # library exports each of them.
 ABI_FUNCTIONS = (
     "smt_last_error", "smt_abi_version", "smt_wgrad_workspace_bytes", "smt_tile_wgrad", "smt_wgrad_batch_workspace_bytes",
@@ -56,6 +56,7 @@ ABI_FUNCTIONS = (
     "smt_beam_last_error", "smt_beam_topk_workspace", "smt_beam_topk",
     "smt_linear_last_error", "smt_linear_skinny_workspace", "smt_linear_skinny", "smt_linear_skinny_bias",
     "smt_linear_skinny_fp8_workspace", "smt_linear_skinny_fp8",
+    "smt_sample_last_error", "smt_sample_workspace", "smt_sample_token",
 )
 
 
@@ -251,6 +252,11 @@ _SIGS = {
                                               ctypes.POINTER(ctypes.c_void_p), _I32, _I32, _P, _P]),
     "smt_linear_skinny_fp8_workspace": (_I64, [_I32, _I32, ctypes.POINTER(SkinnyFp8Out), _I32, _I32]),
     "smt_linear_skinny_fp8": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _I32, ctypes.POINTER(SkinnyFp8Out), _I32, _I32, _P, _P]),
+    "smt_sample_last_error": (ctypes.c_char_p, []),
+    "smt_sample_workspace": (_I64, [_I32, _I64]),
+    "smt_sample_token": (ctypes.c_int, [_P, _I64, _I32, _I32, _I64, _P, _I64, _I32, ctypes.c_float, _P, _I32, ctypes.c_float,
+                                        _I32, ctypes.c_float, ctypes.c_float, _I32, ctypes.c_uint64, ctypes.c_uint32,
+                                        ctypes.c_uint32, _P, _P, _P, _P, _P]),
 }
 
 
@@ -309,6 +315,8 @@ def _check(rc: int, what: str) -> None:
             err = lib.smt_beam_last_error              # beam_kernels.hip
         elif what.startswith("smt_linear"):
             err = lib.smt_linear_last_error            # linear_kernels.hip
+        elif what.startswith("smt_sample"):
+            err = lib.smt_sample_last_error            # sample_kernels.hip
         else:
             err = lib.smt_last_error
         raise RuntimeError(f"{what} failed (status {rc}): {err().decode(errors='replace')}")

@@ -6,7 +6,8 @@ The library is the only native product code: ``csrc/smt_kernels.hip`` (the SMT h
 ``include/smt_attention.h``) and ``csrc/fp8_kernels.hip`` (e4m3 quantisation of the fp8 path, C ABI
 ``include/smt_fp8.h``) and ``csrc/beam_kernels.hip`` (the beam-search scoring step, C ABI
 ``include/smt_beam.h``) and ``csrc/linear_kernels.hip`` (the decode linears, C ABI
-``include/smt_linear.h``) compiled for ``--offload-arch=gfx950``. It is loaded with
+``include/smt_linear.h``) and ``csrc/sample_kernels.hip`` (token selection for ``num_beams == 1``, C ABI
+``include/smt_sample.h``) compiled for ``--offload-arch=gfx950``. It is loaded with
 ctypes by :mod:`sparse_matrix_tuning_amd._hip` (no torch types cross the boundary).
 """
 from __future__ import annotations
@@ -19,9 +20,11 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 SRCS = [os.path.join(PKG_DIR, "csrc", n) for n in ("smt_kernels.hip", "llama_kernels.hip", "attn_kernels.hip",
-                                                   "fp8_kernels.hip", "beam_kernels.hip", "linear_kernels.hip")]
+                                                   "fp8_kernels.hip", "beam_kernels.hip", "linear_kernels.hip",
+                                                   "sample_kernels.hip")]
 HEADERS = [os.path.join(REPO_DIR, "include", n) for n in ("smt_hip.h", "smt_model_ops.h", "smt_attention.h",
-                                                          "smt_fp8.h", "smt_beam.h", "smt_linear.h")]
+                                                          "smt_fp8.h", "smt_beam.h", "smt_linear.h",
+                                                          "smt_sample.h")]
 HEADERS += [os.path.join(PKG_DIR, "csrc", n) for n in ("silu_math.h", "fp8_math.h")]
 LIB_DIR = os.path.join(PKG_DIR, "_lib")
 LIB_PATH = os.path.join(LIB_DIR, "libsmt_hip.so")
